@@ -12,10 +12,16 @@ WORLD_SIZE / MASTER_PORT are read from the environment); each rank owns its own 
 timed region - RCCL inside libmpc_amd.so (mpc_allgather_log).  No PyTorch anywhere: the solver, the
 collective, the barrier and the device synchronisation are all the library's, through ctypes.
 
-Timing.  The K steps from t = 0 (inputs resident in HBM) are bracketed by barrier + device sync on both
-sides, maximum over the ranks.  One such region lasts a few milliseconds, so it is repeated R times
-from the restored initial state (restore untimed) until about a second of GPU time has been spent;
-`value` and `ms_per_step` are the MEDIAN region, `repeats` = R.  The W warm-up steps run first.
+Timing.  The K = --steps steps from t = 0 (inputs resident in HBM) are one timed region, bracketed by
+barrier + device sync on both sides, maximum over the ranks: K is the number of timed steps, and
+`ms_per_step` is the region's time over K.  --repeats R times R such regions from the restored initial
+state (restore untimed; --repeats 0: as many as fill --min-seconds), `value` and `ms_per_step` are then
+the MEDIAN region, `repeats` = R.  The W warm-up steps run first.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path computed in its last step as
+DIR/<name>.npy (float64; status and iteration words converted): the controls U of every instance (of
+every rank, all-gathered, for N > 1) and the loop's other logs and state of that step.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the fused closed-loop kernel against HBM with the
 algorithmic bytes of SURVEY.md section 8d (4 968 B per instance-step); `traffic` is the measured HBM-side
@@ -135,12 +141,40 @@ def cpu_quota():
     return {"affinity_threads": aff, "cgroup_quota_cores": q}
 
 
+def host_oracle_lib(name):
+    """The oracle's -O3 -march=native library ``name`` (a target of oracle/Makefile) for the timed CPU baselines: built for the host that runs
+    the benchmark, from a copy of oracle/'s Makefile and C sources in a temporary directory of this process (the checkout may be read-only
+    where the benchmark runs), removed when the process ends."""
+    import atexit
+    import shutil
+    import subprocess
+    import tempfile
+    d = tempfile.mkdtemp(prefix="mpc_bench_oracle_")
+    atexit.register(shutil.rmtree, d, True)
+    src = os.path.join(ROOT, "oracle")
+    for f in os.listdir(src):
+        if f == "Makefile" or f.endswith((".c", ".h")):
+            shutil.copy(os.path.join(src, f), d)
+    subprocess.check_call(["make", "-C", d, "-s", name])
+    return os.path.join(d, name)
+
+
+def host_oracle(module, cls, name, *args):
+    """``module.cls(*args, fast=True)`` on host_oracle_lib(name): the class loads ``module.build(fast)``, pointed here at that library."""
+    build, lib = module.build, host_oracle_lib(name)
+    module.build = lambda fast=False: lib
+    try:
+        return getattr(module, cls)(*args, fast=True)
+    finally:
+        module.build = build
+
+
 def cpu_baseline(problem, x0, nsteps, target_seconds=8.0, max_seconds=25.0):
     """Time the oracle's C restatement on the host cores: the same closed loop (same instances, same steps, from
     t=0), on all cores and on one, each a bounded sample."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle_c
-    oc = oracle_c.OracleC(problem, lib_path=oracle_c.build_fast())
+    oc = oracle_c.OracleC(problem, lib_path=host_oracle_lib("libmpc_oracle_fast.so"))
     nthr = oc.max_threads()
 
     def run(nb, threads, budget):
@@ -175,6 +209,25 @@ def cpu_baseline(problem, x0, nsteps, target_seconds=8.0, max_seconds=25.0):
                        f"{sorted(tried)} tried ({nthr} hardware threads) "
                        f"(single core: {nb1} instances, {r1} repetitions, {s1:.1f} s): oracle/mpc_oracle.c, a C port of the same Riccati-PDIP with the "
                        f"same warm start, gcc -O3 -march=native -fopenmp built on this host; the reference's own CasADi/IPOPT path is not installable here")
+
+
+DUMP_LIMIT_BYTES = 60_000_000      # under 64 MB with the files' headers
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array [instances, ...] of the timed path's last step as <dirname>/<name>.npy, float64.  Over 64 MB in all, the
+    same fixed, seeded sample of instances is taken of every array and its indices are written as instance_index.npy."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = len(next(iter(arrays.values())))
+        keep = int(n * (DUMP_LIMIT_BYTES - 8 * n) / total)
+        idx = np.sort(np.random.default_rng(SEED).choice(n, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["instance_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(a))
 
 
 def launch_ranks(args):
@@ -344,6 +397,7 @@ def main_enmpc(args):
         if (args.repeats > 0 and len(times) >= args.repeats) or (args.repeats == 0 and (spent >= args.min_seconds or len(times) >= 2000)):
             break
     dt = float(np.median(times))
+    allU = None
     if comm is not None:
         allU = s.allgather_log("U", 0, K)
         assert np.array_equal(allU[rank], s.get_log("U")[:K]), "all-gather of U corrupted the data"
@@ -400,7 +454,7 @@ def main_enmpc(args):
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import enmpc_oracle as eo
             import enmpc_oracle_c as eoc
-            oc = eoc.OracleEC(eo.load_problem(m.example_path("reactor_enmpc.py"), overrides=cfg["over"]), fast=True)      # -O3 -march=native, built on this host
+            oc = host_oracle(eoc, "OracleEC", "libenmpc_oracle_fast.so", eo.load_problem(m.example_path("reactor_enmpc.py"), overrides=cfg["over"]))      # -O3 -march=native, built on this host
             nthr = oc.max_threads()
             t0 = time.perf_counter(); oc.closed_loop(K, x0[:2], nthreads=1, logs=False); r1 = 2 * K / (time.perf_counter() - t0)      # one core, to size the samples
             tried, est = {}, None
@@ -420,6 +474,11 @@ def main_enmpc(args):
         import ctypes
         sys.stdout.flush(); ctypes.CDLL(None).fflush(None)
         print(json.dumps(out), flush=True)
+        if args.dump_outputs:      # every log of the last timed step (the controls of all ranks when gathered)
+            logs = {k: s.get_log(k)[K - 1] for k in list(s.LOGS) + list(s.ILOGS)}
+            if comm is not None:
+                logs["U"] = allU[:, K - 1].reshape(-1, allU.shape[-1])
+            dump_outputs(args.dump_outputs, logs)
     if comm is not None:
         comm.barrier()
     s.close()
@@ -515,7 +574,7 @@ def main_nmpc(args):
         import nmpc_oracle_c as noc
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            oc = noc.OracleNC(no.load_problem(m.example_path("cstr_nmpc.py")), fast=True)      # the checker's own reading of the example; -O3 -march=native, built on this host
+            oc = host_oracle(noc, "OracleNC", "libnmpc_oracle_fast.so", no.load_problem(m.example_path("cstr_nmpc.py")))      # the checker's own reading of the example; -O3 -march=native, built on this host
         nthr = oc.max_threads()
         t0 = time.perf_counter(); oc.closed_loop(K, x0[:2], max_sqp=args.max_sqp, nthreads=1, logs=False); r1 = 2 * K / (time.perf_counter() - t0)
         tried, est = {}, None
@@ -529,6 +588,8 @@ def main_nmpc(args):
                                          "oracle/nmpc_oracle.c - EKF, target SQP and one SQP iteration of the OCP per step with complex-step Jacobians and dense null-space "
                                          "(QR + Cholesky) interior-point QP solves, gcc -O3 -march=native -fopenmp built on this host; the reference's CasADi/IPOPT path is "
                                          "not installable here" % (tried[best][1], K, best, sorted(tried), nthr)}
+    if args.dump_outputs:      # every log of the last timed step
+        dump_outputs(args.dump_outputs, {k: s.get_log(k)[K - 1] for k in list(s.LOGS) + list(s.ILOGS)})
     print(json.dumps(out), flush=True)
     s.close()
 
@@ -543,9 +604,8 @@ def main():
                     "0: --batch instances per GPU (weak scaling, the default)")
     ap.add_argument("--steps-per-launch", type=int, default=0, help="closed-loop steps per kernel launch (0: library default)")
     ap.add_argument("--loop-kernel", type=int, default=0, help="0: library default, 1: instance per lane, 2: horizon-parallel, 3: wave-autonomous")
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions (0: as many as fill --min-seconds)")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="GPU time to spend in timed regions (of this workload and of each of the other configs' child runs: "
-                                                                   "twelve seconds of busy GPU in the default run, which a utilisation sampler can see between the CPU baselines)")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of --steps steps each, the median reported (0: as many as fill --min-seconds)")
+    ap.add_argument("--min-seconds", type=float, default=3.0, help="with --repeats 0: GPU time to spend in timed regions (of this workload and of each of the other configs' child runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-dist", action="store_true", help="create the RCCL communicator even for one rank: exercises the N>1 code path on a 1-GPU box")
     ap.add_argument("--config", default="lmpc", choices=["lmpc", "nmpc", "enmpc", "mhe"], help="lmpc: the metric workload (BASELINE configs[1]); nmpc: "
@@ -556,6 +616,7 @@ def main():
                     "as the profiles need it - overlapping launches have no duration of their own)")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="nmpc / enmpc / mhe: host seconds per thread count of the CPU baseline's bounded sample")
     ap.add_argument("--no-other-configs", action="store_true", help="lmpc on one GPU: do not measure BASELINE configs[2..4] next to the metric workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: every rank goes through the rendezvous only and rank 0 prints who was there (launcher test)")
     args = ap.parse_args()
     launch_ranks(args)                # --gpus N without a launcher: N child processes, one per GPU (before anything here touches the GPU)
@@ -679,6 +740,12 @@ def main():
         allU = solver.allgather_log("U", 0, K)
         assert np.array_equal(allU[rank], solver.loop_get_log("U")[:K]), "all-gather of U corrupted the data"
         comm.barrier()
+    if args.dump_outputs:      # the last timed step: the all-gathered controls (what the timed path hands its caller), status words, the loop state it left
+        lastU = solver.allgather_log("U", K - 1, 1)      # every rank takes part: a collective for N > 1
+        if rank == 0:
+            state = solver.loop_get_state()
+            dump_outputs(args.dump_outputs, {"U": lastU.reshape(-1, prob.nu), "STATUS_DYN": st[K - 1], "ITERS_DYN": it[K - 1],
+                                             **{k: state[k] for k in ("x_p", "xhat", "dhat", "P", "xs", "us")}})
     solver.close()
     if rank == 0:
         # the one JSON line is the last thing on stdout: whatever a native library left in C's stdio buffer goes out first

@@ -9,8 +9,6 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-REF = "/root/reference"
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
@@ -30,6 +28,13 @@ def gpu_available():
 def pkg():
     import mpc_code_amd
     return mpc_code_amd
+
+
+@pytest.fixture(scope="session")
+def ref_gold():
+    """The reference's Ex-files as the loaders read them (tests/golden/reference_examples.npz, tests/reference_golden.py)."""
+    import reference_golden
+    return reference_golden.load()
 
 
 @pytest.fixture(scope="session")

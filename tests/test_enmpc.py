@@ -14,7 +14,8 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import REF, ROOT
+from conftest import ROOT
+from reference_golden import assert_fields
 
 import enmpc_oracle as eo
 
@@ -193,16 +194,15 @@ def test_estimator_nlp_of_this_example_is_a_convex_qp_with_the_oracles_answer(op
     assert np.abs(qp["w"] - sol["w"]).max() < 1e-8
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "Ex_ENMPC.py")), reason="reference tree not present")
-def test_repo_example_is_the_reference_example(oprob, pkg):
-    """mpc-code_amd/examples/reactor_enmpc.py poses the problem of the reference's Ex_ENMPC.py: the oracle gives bit-equal loops on
-    the two files, and the product's loader takes the reference file unmodified."""
-    ref = eo.load_problem(os.path.join(REF, "Ex_ENMPC.py"))
-    a, b = eo.closed_loop(oprob, 3), eo.closed_loop(ref, 3)
+def test_repo_example_is_the_reference_example(oprob, pkg, ref_gold):
+    """mpc-code_amd/examples/reactor_enmpc.py poses the problem of the reference's Ex_ENMPC.py: the oracle gives the loops it gave on the
+    reference's file (tests/golden/reference_examples.npz; to rounding, as the vectors were computed on another host), and the product's
+    loader read the reference file unmodified to what it reads of this one."""
+    a = eo.closed_loop(oprob, 3)
     for k in ("U", "XS", "US", "X_ES", "P_K"):
-        assert np.array_equal(a[k], b[k]), k
-    q = pkg.load_problem(os.path.join(REF, "Ex_ENMPC.py"), overrides={"N": 40, "N_mhe": 20})
-    assert (q.N, q.N_mhe, q.nx, q.nu, q.n_w, q.max_iter) == (40, 20, 2, 1, 4, 200)
+        assert np.abs(a[k] - ref_gold["enmpc_loop_" + k]).max() < 1e-12, k
+    q = pkg.load_problem(EX, overrides={"N": 40, "N_mhe": 20})
+    assert (q.N, q.N_mhe, q.nx, q.nu, q.n_w, q.max_iter) == tuple(ref_gold["enmpc_N40"].tolist()) == (40, 20, 2, 1, 4, 200)
 
 
 def test_extended_kalman_filter_variant_restatements_agree_and_reproduce_their_vectors():
@@ -290,21 +290,19 @@ def test_estimator_with_bounded_state_noise_restatements_agree():
     assert int(r["STATUS_MHE"].max()) == 0 and np.abs(r["X_ES"] - r0["X_ES"]).max() > 0.05
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "Ex_ENMPC.py")), reason="reference tree not present")
-def test_reference_example_with_its_estimator_switch_off_is_the_filter_variant(pkg, tmp_path):
+def test_reference_example_with_its_estimator_switch_off_is_the_filter_variant(pkg, ref_gold):
     """The switch is a source line of the reference's file (mhe_mod = 'on', Ex_ENMPC.py:109), evaluated while the file runs: a copy with that one line changed
-    loads in both loaders as the extended-Kalman-filter problem and gives the loops of mpc-code_amd/examples/reactor_enmpc_ekf.py to the bit."""
-    src = open(os.path.join(REF, "Ex_ENMPC.py")).read()
-    assert src.count("mhe_mod = 'on'") == 1
-    f = tmp_path / "Ex_ENMPC_ekf.py"
-    f.write_text(src.replace("mhe_mod = 'on'", "mhe_mod = 'off'"))
-    ref, own = eo.load_problem(str(f)), eo.load_problem(EX_EKF)
-    assert ref.ekf and not ref.mhe and np.array_equal(ref.Q_kf, own.Q_kf) and np.array_equal(ref.R_kf, own.R_kf) and np.array_equal(ref.P0, own.P0)
-    a, b = eo.closed_loop(own, 3), eo.closed_loop(ref, 3)
+    loaded in both loaders as the extended-Kalman-filter problem (tests/golden/make_reference_golden.py) and gives the loops of
+    mpc-code_amd/examples/reactor_enmpc_ekf.py (to rounding: the stored loops were computed on another host)."""
+    own = eo.load_problem(EX_EKF)
+    assert ref_gold["ekf_flags"].tolist() == [True, False] and own.ekf and not own.mhe
+    assert_fields(own, ref_gold, "ekf_", ("Q_kf", "R_kf", "P0"))
+    a = eo.closed_loop(own, 3)
     for k in ("U", "XS", "US", "X_ES", "P_K"):
-        assert np.array_equal(a[k], b[k]), k
-    q = pkg.load_problem(str(f), overrides={"N": 40})
-    assert (q.estimator, q.N, q.nx, q.nu) == ("ekf", 40, 2, 1) and np.array_equal(q.Q_kf, own.Q_kf) and np.array_equal(q.R_kf, own.R_kf)
+        assert np.abs(a[k] - ref_gold["ekf_loop_" + k]).max() < 1e-12, k
+    q = pkg.load_problem(EX_EKF, overrides={"N": 40})
+    assert (q.estimator, q.N, q.nx, q.nu) == (str(ref_gold["ekf_pkg_estimator"]), *ref_gold["ekf_pkg_dims"].tolist()) == ("ekf", 40, 2, 1)
+    assert np.array_equal(q.Q_kf, ref_gold["ekf_pkg_Q_kf"]) and np.array_equal(q.R_kf, ref_gold["ekf_pkg_R_kf"])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -1,13 +1,9 @@
 """Ex-file surface: the loader runs Ex-style files without CasADi and yields the reference's problem."""
-import os
-
 import numpy as np
 import pytest
 
-from conftest import REF
-
-FIELDS = ["A", "B", "C", "Bd", "Cd", "Ap", "Bp", "Cp", "Q", "R", "P", "Qss", "Rss", "umin", "umax", "xmin", "xmax",
-          "ymin", "ymax", "x0_p", "x0_m", "u0", "fx_const", "fy_const", "Q_kf", "R_kf", "P0"]
+from reference_golden import EX_FIELDS as FIELDS
+from reference_golden import EX_FILES, KIND_REFUSALS, assert_fields
 
 
 def test_cstr_dimensions_and_flags(cstr):
@@ -36,41 +32,39 @@ def test_schedules_follow_callbacks(cstr):
     assert np.array_equal(s["pyp"][7], [0.1, 0.1, 0])                                               # :59-79
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("ours,theirs", [("cstr_lmpc.py", "Ex_LMPC_CSTR.py"), ("wood_berry_lmpc.py", "Ex_LMPC_WB.py"),
                                          ("cstr_nlplant_lmpc.py", "Ex_LMPC_nlplant.py"),
                                          ("cstr_xp_nlplant_lmpc.py", "Ex_LMPCxp_nlplant.py")])
-def test_unmodified_reference_examples_load_to_the_same_problem(pkg, ours, theirs):
+def test_unmodified_reference_examples_load_to_the_same_problem(pkg, ref_gold, ours, theirs):
+    """The loader's reading of the reference's unmodified Ex-file (tests/golden/reference_examples.npz) and of ours: one problem."""
     a = pkg.load_problem(pkg.example_path(ours))
-    b = pkg.load_problem(os.path.join(REF, theirs))
-    for f in FIELDS:
-        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    pre = "ex_" + theirs[:-3] + "_"
+    assert_fields(a, ref_gold, pre, FIELDS)
     for t in (0, 10, 11, 15, 16, 20, 21, 99):
-        for x, y in zip(a.defSP(t), b.defSP(t)):
-            assert np.array_equal(np.ravel(x), np.ravel(y))
-    assert a.estimator == b.estimator and a.DUForm == b.DUForm and a.N == b.N == 50
-    assert a.plant_is_linear == b.plant_is_linear
-    if not a.plant_is_linear:      # the two plant functions integrate to the same states, bit for bit
-        rng = np.random.default_rng(0)
-        x = a.x0_p + rng.normal(size=(5, a.nxp)) * [0.01, 2.0, 0.01]; u = a.u0 + rng.normal(size=(5, a.nu)) * [2.0, 0.01]
-        assert np.array_equal(a.plant_step(x, u, 0.4, np.zeros(a.nxp)), b.plant_step(x, u, 0.4, np.zeros(a.nxp)))
+        for i, x in enumerate(a.defSP(t)):
+            assert np.array_equal(np.ravel(x), ref_gold[f"{pre}sp{t}_{i}"])
+    assert a.estimator == str(ref_gold[pre + "estimator"]) and [a.DUForm, a.N, a.plant_is_linear] == ref_gold[pre + "flags"].tolist() and a.N == 50
+    if not a.plant_is_linear:      # the two plant functions integrate to the same states (to rounding: the stored states were computed on another host)
+        x, u = ref_gold[pre + "plant_x"], ref_gold[pre + "plant_u"]
+        np.testing.assert_allclose(a.plant_step(x, u, 0.4, np.zeros(a.nxp)), ref_gold[pre + "plant"], rtol=1e-13, atol=0)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
-def test_every_example_of_the_reference_loads_unmodified(pkg):
-    """All seven Ex_*.py files of the reference go through load_problem as they are (round 3: the economic one too); features no path
-    carries are still refused loudly."""
-    import glob, warnings
-    kinds = {}
-    for f in sorted(glob.glob(os.path.join(REF, "Ex_*.py"))):
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            kinds[os.path.basename(f)] = type(pkg.load_problem(f)).__name__
+def test_every_example_of_the_reference_loads_unmodified(pkg, ref_gold):
+    """All seven Ex_*.py files of the reference went through load_problem as they are (round 3: the economic one too; recorded in
+    tests/golden/reference_examples.npz), and their counterparts here load to the same problem classes; features no path carries are
+    still refused loudly."""
+    import warnings
+    kinds = dict(zip(ref_gold["kinds_files"].tolist(), ref_gold["kinds_types"].tolist()))
     assert kinds == {"Ex_ENMPC.py": "EconomicMPCProblem", "Ex_LMPC_CSTR.py": "LinearMPCProblem", "Ex_LMPC_WB.py": "LinearMPCProblem", "Ex_LMPC_nlplant.py": "LinearMPCProblem",
                      "Ex_LMPCxp_nlplant.py": "LinearMPCProblem", "Ex_NMPC.py": "NonlinearMPCProblem", "Ex_NMPC_dis.py": "NonlinearMPCProblem"}, kinds
-    for over in ({"slacks": True}, {"Collocation": True}, {"mhe_up": "other"}):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        ours = {theirs: type(pkg.load_problem(pkg.example_path(f))).__name__ for theirs, f in EX_FILES.items()}
+    assert ours == kinds, ours
+    assert ref_gold["kinds_refused"].tolist() == [True] * len(KIND_REFUSALS)
+    for over in KIND_REFUSALS:
         with pytest.raises(pkg.UnsupportedProblem):
-            pkg.load_problem(os.path.join(REF, "Ex_ENMPC.py"), overrides=over)
+            pkg.load_problem(pkg.example_path("reactor_enmpc.py"), overrides=over)
 
 
 def test_overrides_apply_after_the_file(pkg):

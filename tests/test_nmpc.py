@@ -11,7 +11,8 @@ import re
 import numpy as np
 import pytest
 
-from conftest import REF, ROOT, gpu_available
+from conftest import ROOT, gpu_available
+from reference_golden import DIS_FIELDS, NMPC_FIELDS, RX_POINT, assert_fields
 
 GOLD = os.path.join(ROOT, "tests", "golden", "nmpc_cstr.npz")
 
@@ -98,21 +99,16 @@ def test_if_else_is_traced_as_a_select(nl):
     assert abs(a - x[0, 2]) < 1e-12 and b > a + 1e-3 and c < a - 1e-3      # level: steady, filling (0.15 in), draining (0.08 in)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
-def test_same_problem_as_the_reference_example(pkg, nl, onl):
-    """The reference's Ex_NMPC.py loads unmodified and defines the same problem as examples/cstr_nmpc.py."""
-    ref = pkg.load_problem(os.path.join(REF, "Ex_NMPC.py"), overrides={"N": 30})
-    for k in ("Q", "R", "Qss", "Rss", "umin", "umax", "xmin", "xmax", "ymin", "ymax", "dmin", "dmax", "Q_kf", "R_kf", "P0", "x0_p", "x0_m",
-              "u0", "dhat0", "umin_ss", "umax_ss", "xmin_ss", "xmax_ss", "ymin_ss", "ymax_ss"):
-        assert np.array_equal(getattr(ref, k), getattr(nl, k)), k
-    assert (ref.nx, ref.nu, ref.ny, ref.nd, ref.nxp, ref.h, ref.Mx, ref.Nsim, ref.ycols) == (nl.nx, nl.nu, nl.ny, nl.nd, nl.nxp, nl.h, nl.Mx, nl.Nsim, nl.ycols)
+def test_same_problem_as_the_reference_example(pkg, nl, onl, ref_gold):
+    """The reference's Ex_NMPC.py loaded unmodified (tests/golden/reference_examples.npz) and defines the same problem as examples/cstr_nmpc.py."""
+    assert_fields(nl, ref_gold, "nmpc_", NMPC_FIELDS)
+    assert [nl.nx, nl.nu, nl.ny, nl.nd, nl.nxp, nl.h, nl.Mx, nl.Nsim] == ref_gold["nmpc_dims"].tolist() and np.array_equal(np.asarray(nl.ycols), ref_gold["nmpc_ycols"])
     import nmpc_oracle as no
-    x, u, d = sample(nl, 4, seed=2)
+    x, u, d = ref_gold["nmpc_x"], ref_gold["nmpc_u"], ref_gold["nmpc_d"]
     for i in range(4):
-        oref = oracle_problem(os.path.join(REF, "Ex_NMPC.py"), {"N": 30})
-        assert np.allclose(no.model_fx(oref, x[i], u[i], d[i]), no.model_fx(onl, x[i], u[i], d[i]), rtol=1e-13, atol=0)
-        for t in (0.0, 7.0, 30.0):
-            assert np.allclose(no.plant_fx(oref, x[i], u[i], t), no.plant_fx(onl, x[i], u[i], t), rtol=1e-13, atol=0)
+        assert np.allclose(ref_gold["nmpc_model_fx"][i], no.model_fx(onl, x[i], u[i], d[i]), rtol=1e-13, atol=0)
+        for j, t in enumerate((0.0, 7.0, 30.0)):
+            assert np.allclose(ref_gold["nmpc_plant_fx"][i, j], no.plant_fx(onl, x[i], u[i], t), rtol=1e-13, atol=0)
     for k in ("Q", "R", "Qss", "Rss", "umin", "umax", "xmin", "xmax", "ymin", "ymax", "dmin", "dmax", "Q_kf", "R_kf", "P0", "x0_p", "x0_m", "u0", "dhat0"):
         assert np.array_equal(getattr(onl, k), getattr(nl, k)), k      # two independent loaders, one problem
 
@@ -502,21 +498,18 @@ def test_traced_discrete_model_equals_the_user_function(qt):
     assert np.allclose(J, A, rtol=1e-6, atol=1e-8) and np.allclose(J[:2], 0.0) and np.allclose(G, qt.Bd)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
-def test_same_problem_as_the_reference_discrete_example(pkg, qt):
-    ref = pkg.load_problem(os.path.join(REF, "Ex_NMPC_dis.py"), overrides={"N": 20})
-    for k in ("Q", "R", "Qss", "Rss", "umin", "umax", "xmin", "xmax", "ymin", "ymax", "Dumin", "Dumax", "K", "Pf", "Bd", "Cd", "x0_p", "x0_m", "u0", "dhat0"):
-        assert np.array_equal(getattr(ref, k), getattr(qt, k)), k
-    assert (ref.estimator, ref.DUForm, ref.DUssForm, ref.ycols, ref.Nsim, ref.discrete) == (qt.estimator, qt.DUForm, qt.DUssForm, qt.ycols, qt.Nsim, qt.discrete)
+def test_same_problem_as_the_reference_discrete_example(pkg, qt, ref_gold):
+    """The reference's Ex_NMPC_dis.py loaded unmodified (tests/golden/reference_examples.npz) and defines the problem of examples/quadtank_nmpc_dis.py."""
+    assert_fields(qt, ref_gold, "dis_", DIS_FIELDS)
+    assert qt.estimator == str(ref_gold["dis_estimator"]) and [qt.DUForm, qt.DUssForm, qt.Nsim, qt.discrete] == ref_gold["dis_flags"].tolist()
+    assert np.array_equal(np.asarray(qt.ycols), ref_gold["dis_ycols"])
     import nmpc_oracle as no
-    rng = np.random.default_rng(1)
-    for x in [qt.x0_m + rng.normal(size=6) * [3, 3, 2, 2, 0.5, 0.5] for _ in range(3)] + [np.array([50, 50, 25.0, -1.0, 0.2, 19.99]), np.array([50, 50, 19.9, 0.01, 22, 0.0])]:
-        u = qt.u0 + rng.normal(size=2) * 5
-        oref, oqt = oracle_problem(os.path.join(REF, "Ex_NMPC_dis.py"), {"N": 20}), oracle_problem("quadtank_nmpc_dis.py")
-        assert np.allclose(no.model_fx(oref, x, u, np.zeros(2)), no.model_fx(oqt, x, u, np.zeros(2)), rtol=1e-13, atol=1e-13)       # clamping included
-        assert np.allclose(no.plant_fx(oref, x, u, 100.0), no.plant_fx(oqt, x, u, 100.0), rtol=1e-13, atol=1e-13)
+    oqt = oracle_problem("quadtank_nmpc_dis.py")
+    for i, (x, u) in enumerate(zip(ref_gold["dis_x"], ref_gold["dis_u"])):
+        assert np.allclose(ref_gold["dis_model_fx"][i], no.model_fx(oqt, x, u, np.zeros(2)), rtol=1e-13, atol=1e-13)       # clamping included
+        assert np.allclose(ref_gold["dis_plant_fx"][i], no.plant_fx(oqt, x, u, 100.0), rtol=1e-13, atol=1e-13)
     for t in (10, 60, 1500, 2500, 3500, 4500, 6000):
-        assert all(np.array_equal(a_, b_) for a_, b_ in zip(ref.defSP(t), qt.defSP(t))) and np.array_equal(ref.def_pxp(t)[0], qt.def_pxp(t)[0])
+        assert all(np.array_equal(b_, ref_gold[f"dis_sp{t}_{i}"]) for i, b_ in enumerate(qt.defSP(t))) and np.array_equal(qt.def_pxp(t)[0], ref_gold[f"dis_pxp{t}"])
 
 
 def test_discrete_oracle_reproduces_its_golden_rows(qt_mild):
@@ -575,7 +568,7 @@ def rx(pkg):
     return pkg.load_problem(pkg.example_path("reactor_nmpc.py"))
 
 
-def test_reactor_example_is_classified_and_its_model_is_the_reference_reactor(pkg, rx):
+def test_reactor_example_is_classified_and_its_model_is_the_reference_reactor(pkg, rx, ref_gold):
     """nx = 2, nu = 1: the smallest stage (the wave-style kernels take it: state <= 4, nu <= 2); continuous model, EKF, disturbances
     inside the model.  With the disturbances at zero the model is the reactor of the reference's Ex_ENMPC.py (:42-49,64-65)."""
     from mpc_code_amd import nlcodegen
@@ -589,11 +582,9 @@ def test_reactor_example_is_classified_and_its_model_is_the_reference_reactor(pk
     d = np.array([0.1, -0.05])      # the two disturbances: rate constant of the first reaction, dilution rate
     want_d = [0.65 * (1.0 - 0.4) - 1.1 * 0.4, -0.65 * 0.55 + 1.1 * 0.4 - 0.05 * 0.55]
     assert np.allclose([float(v) for v in st.evaluate(rx.f, rx._vals(x=x, u=u, d=d, t=0.0))], want_d, rtol=1e-14)
-    if os.path.isdir(REF):          # the same balances as the reference's file, traced from its own function
-        ref = pkg.load_exfile(os.path.join(REF, "Ex_ENMPC.py"))
-        fx = ref["User_fxm_Cont"](st.symvec("x", 2), st.symvec("u", 1), st.symvec("d", 2), st.Sym.var("t"), None)
-        vals = {"x[0]": 0.4, "x[1]": 0.55, "u[0]": 0.7, "d[0]": 0.0, "d[1]": 0.0, "t": 0.0}
-        assert np.allclose([float(v) for v in st.evaluate(list(fx), vals)], want, rtol=1e-14)
+    # the same balances as the reference's file, traced from its own function at this point (tests/golden/reference_examples.npz)
+    assert RX_POINT == {"x[0]": 0.4, "x[1]": 0.55, "u[0]": 0.7, "d[0]": 0.0, "d[1]": 0.0, "t": 0.0}
+    assert np.allclose(ref_gold["rx_fx"], want, rtol=1e-14)
 
 
 def test_reactor_oracle_reproduces_its_golden_rows(rx):

@@ -1,4 +1,4 @@
-import sys, time; sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/oracle')
+import os, sys, time; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import numpy as np, mpc_code_amd as m
 from mpc_code_amd import capi
 import oracle_c

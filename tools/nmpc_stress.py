@@ -1,8 +1,8 @@
 """Non-linear path: the three kernels on ragged batches with model / plant mismatch and wide initial boxes (holds, infeasible steps):
    tools/nmpc_stress.py"""
-import sys, warnings, numpy as np
+import os, sys, warnings, numpy as np
 warnings.filterwarnings("ignore")
-sys.path.insert(0,'/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mpc_code_amd as m
 from mpc_code_amd import nmpc
 p = m.load_problem(m.example_path("cstr_nmpc.py"))

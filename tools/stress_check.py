@@ -1,6 +1,6 @@
 import os, sys, time
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import mpc_code_amd as m
 from mpc_code_amd import capi
