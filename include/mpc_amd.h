@@ -89,6 +89,20 @@ typedef struct mpc_lin_desc {
      * variable of its own).  n_user_rows = 0: none.  Not together with slacks, term_cons or px / py. */
     int32_t n_user_rows;
     const double *Gx, *Gu, *Gd, *g0;
+    /* Affine user inequality rows of the TARGET problem (User_g_ineq_SS, Target_Calc.py:87-99,105-108,149-155; MPC_code.py:295-300):
+     *     Gx_ss xs + Gu_ss us + Gd_ss dhat + g0_ss <= 0     (Gx_ss [n][nx], Gu_ss [n][nu], Gd_ss [n][nd], g0_ss [n], row-major; the reference's Ys = C xs + Cd dhat + fy_const
+     *                                                         substituted by the caller, Target_Calc.py:75-81)
+     * 0 <= n_ss_ineq_rows <= 4; 0: none.  They are rows of the target QP only (the OCP does not see them), with the bounds (-inf, 0]. */
+    int32_t n_ss_ineq_rows;
+    const double *Gx_ss, *Gu_ss, *Gd_ss, *g0_ss;
+    /* Affine user equality rows of the target problem (User_h_eq_SS, Target_Calc.py:91-93,100-109,149-150; MPC_code.py:295-300):
+     *     Hx_ss xs + Hu_ss us + Hd_ss dhat + h0_ss = 0      (Hx_ss [n][nx], Hu_ss [n][nu], Hd_ss [n][nd], h0_ss [n], row-major; ys substituted as above)
+     * 0 <= n_ss_eq_rows < nu (the target keeps a free direction); [A-I, B; Hx_ss, Hu_ss] must have full row rank, and the target's reduced Hessian on its null space
+     * must be positive definite (mpc_lin_create returns -4 otherwise, -1 when a pointer is missing).  Neither kind of row together with model offsets
+     * (mpc_set_model_offsets, mpc_loop_set_model_schedule: -8).  A target the rows leave infeasible is status 2, and the closed loop keeps the previous one
+     * (MPC_code.py:714). */
+    int32_t n_ss_eq_rows;
+    const double *Hx_ss, *Hu_ss, *Hd_ss, *h0_ss;
 } mpc_lin_desc;
 
 /* Replaces the construction nlpsol('solver','ipopt',...) of Control_Calc.py:256-258 and

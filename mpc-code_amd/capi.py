@@ -43,22 +43,31 @@ class _Desc(ct.Structure):
                                    "umin_ss", "umax_ss", "xmin_ss", "xmax_ss", "ymin_ss", "ymax_ss",
                                    "dmin", "dmax", "Q_kf", "R_kf", "K", "Dumin", "Dumax")] + [("term_cons", ct.c_int32), ("nl_plant", ct.c_int32), ("h_sample", ct.c_double),
                                                                                              ("slacks", ct.c_int32), ("Ws", _dp),
-                                                                                             ("n_user_rows", ct.c_int32), ("Gx", _dp), ("Gu", _dp), ("Gd", _dp), ("g0", _dp)]
+                                                                                             ("n_user_rows", ct.c_int32), ("Gx", _dp), ("Gu", _dp), ("Gd", _dp), ("g0", _dp),
+                                                                                             ("n_ss_ineq_rows", ct.c_int32), ("Gx_ss", _dp), ("Gu_ss", _dp), ("Gd_ss", _dp), ("g0_ss", _dp),
+                                                                                             ("n_ss_eq_rows", ct.c_int32), ("Hx_ss", _dp), ("Hu_ss", _dp), ("Hd_ss", _dp), ("h0_ss", _dp)]
+
+
+def _dims_key(dims):
+    """(nx, nu, ny, nd, nxp, du_form, general_output_rows[, ss_ineq_rows, ss_eq_rows]): a set without target rows keeps its seven-entry name."""
+    dims = tuple(int(v) for v in dims)
+    return dims[:7] if len(dims) == 9 and dims[7:] == (0, 0) else dims
 
 
 def jit_library_path(dims) -> str:
-    return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(int(v)) for v in dims) + ".so")
+    return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(v) for v in _dims_key(dims)) + ".so")
 
 
 def plant_library_path(dims, header_text: str) -> str:
     import hashlib
-    return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(int(v)) for v in dims) + "_plant_" + hashlib.sha256(header_text.encode()).hexdigest()[:12] + ".so")
+    return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(v) for v in _dims_key(dims)) + "_plant_" + hashlib.sha256(header_text.encode()).hexdigest()[:12] + ".so")
 
 
 def build_library(force: bool = False, verbose: bool = False, dims=None, plant_header: Optional[str] = None) -> str:
     """Compile ``csrc/mpc_amd.hip`` for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
-    ``dims = (nx, nu, ny, nd, nxp, du_form, general_output_rows)``: a library holding the kernels of exactly that
+    ``dims = (nx, nu, ny, nd, nxp, du_form, general_output_rows[, ss_ineq_rows, ss_eq_rows])`` (the last two: user rows of the
+    target problem, zero when left out): a library holding the kernels of exactly that
     dimension set (every kernel is a template on the problem dimensions; the default library carries the sets of the
     shipped examples, ``mpc_build_info()``), written to ``csrc/jit/`` and reused while the sources are unchanged."""
     srcs = [os.path.join(CSRC, f) for f in ("mpc_amd.hip", "mpc_device.hpp", "mpc_sym.hpp", "mpc_tp.hpp", "mpc_wave.hpp")] + \
@@ -75,7 +84,7 @@ def build_library(force: bool = False, verbose: bool = False, dims=None, plant_h
     flags = list(HIPCC_FLAGS)
     if dims is not None:
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        flags.append("-DMPC_DIM_LIST(X)=X(" + ",".join(str(int(v)) for v in dims) + ")")
+        flags.append("-DMPC_DIM_LIST(X)=X(" + ",".join(str(v) for v in _dims_key(dims)) + ")")
     if hdr is not None:
         with open(hdr, "w") as fh:
             fh.write(plant_header)
@@ -213,6 +222,12 @@ class Solver:
             for k in ("Gx", "Gu", "Gd", "g0"):
                 a = _c(getattr(p, k)); a = a if a.size else np.zeros(1)
                 self._keep[k] = a; setattr(d, k, _p(a))
+        d.n_ss_ineq_rows, d.n_ss_eq_rows = int(getattr(p, "n_ss_ineq_rows", 0)), int(getattr(p, "n_ss_eq_rows", 0))
+        for n_rows, keys in ((d.n_ss_ineq_rows, ("Gx_ss", "Gu_ss", "Gd_ss", "g0_ss")), (d.n_ss_eq_rows, ("Hx_ss", "Hu_ss", "Hd_ss", "h0_ss"))):
+            if n_rows:      # affine User_g_ineq_SS / User_h_eq_SS rows of the target (problem.py:_affine_user_rows)
+                for k in keys:
+                    a = _c(getattr(p, k)); a = a if a.size else np.zeros(1)
+                    self._keep[k] = a; setattr(d, k, _p(a))
         self.fused_plant = False
         if lib_path is None and not p.plant_is_linear and jit and not os.environ.get("MPC_AMD_NO_JIT"):
             # the Ex-file's plant function, traced and compiled into a library of this problem's own (cached under csrc/jit/)
@@ -224,7 +239,7 @@ class Solver:
             if hdr is not None:
                 ng = 0 if getattr(p, "slacks", False) else sum(1 for i in range(p.ny) if p.y_bounded and (np.isfinite(p.ymin[i]) or np.isfinite(p.ymax[i])) and np.count_nonzero(p.C[i]) != 1)
                 ng += int(getattr(p, "n_user_rows", 0))
-                dims = (p.nx, p.nu, p.ny, p.nd, p.nxp, int(p.DUForm or p.Dumin is not None or p.Dumax is not None), ng)
+                dims = (p.nx, p.nu, p.ny, p.nd, p.nxp, int(p.DUForm or p.Dumin is not None or p.Dumax is not None), ng, d.n_ss_ineq_rows, d.n_ss_eq_rows)
                 self.lib = load_library(build_library(dims=dims, plant_header=hdr))
                 d.nl_plant = 1
                 self.fused_plant = True
@@ -246,9 +261,10 @@ class Solver:
             # no kernel compiled for these dimensions: build the library of exactly this set (about a minute of hipcc, then cached
             # under csrc/jit/) - the kernels are templates on the dimensions, any stage state <= 8 and nu <= 4 compiles
             import re
-            m = re.search(r"nx=(\d+) nu=(\d+) ny=(\d+) nd=(\d+) nxp=(\d+) du_form=(\d+) general_output_rows=(\d+)", self.lib.mpc_last_error().decode())
+            m = re.search(r"nx=(\d+) nu=(\d+) ny=(\d+) nd=(\d+) nxp=(\d+) du_form=(\d+) general_output_rows=(\d+)(?: ss_ineq_rows=(\d+) ss_eq_rows=(\d+))?",
+                          self.lib.mpc_last_error().decode())
             if m:
-                self.lib = load_library(build_library(dims=tuple(int(v) for v in m.groups())))
+                self.lib = load_library(build_library(dims=tuple(int(v) for v in m.groups() if v is not None)))
                 rc = self.lib.mpc_lin_create(ct.byref(d), ct.byref(self.h))
         if rc != 0:
             self.h = None

@@ -55,9 +55,12 @@ extern "C" const char *mpc_last_error(void) { return g_err; }
 #endif
 
 // ---------------------------------------------------------------------------------------------------
-// compiled dimension sets: NX, NU, NY, ND, NXP, DU, NG  (NG = bounded output rows that are not a multiple of one state;
-// each is carried as one more stage state, see build_problem)
+// compiled dimension sets: NX, NU, NY, ND, NXP, DU, NG[, NGS, NHS]  (NG = bounded output rows that are not a multiple of one state;
+// each is carried as one more stage state, see build_problem.  NGS / NHS = inequality / equality user rows of the target problem,
+// User_g_ineq_SS / User_h_eq_SS, see build_target; a set that leaves them out has none: MPC_DIM9 supplies 0, 0)
 // ---------------------------------------------------------------------------------------------------
+#define MPC_DIM9_(M, NX, NU, NY, ND, NXP, DU, NG, NGS, NHS, ...) M(NX, NU, NY, ND, NXP, DU, NG, NGS, NHS)
+#define MPC_DIM9(M, ...) MPC_DIM9_(M, __VA_ARGS__, 0, 0, 0)
 #ifndef MPC_DIM_LIST
 #define MPC_DEFAULT_DIM_LIST 1
 // The default library is built from two objects compiled side by side (capi.build_library: this file with -DMPC_HAVE_PART2 and with -DMPC_PART2):
@@ -273,7 +276,7 @@ struct TargetArgs {
     int B; size_t Bs;
 };
 
-template <int NX, int NU, int NY, int ND>
+template <int NX, int NU, int NY, int ND, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64) void target_kernel(const DevProblem *__restrict__ Pp, TargetArgs a)
 {
     const int b = blockIdx.x * 64 + threadIdx.x;
@@ -287,7 +290,7 @@ __global__ __launch_bounds__(64) void target_kernel(const DevProblem *__restrict
     double px0[NX], py0[NY];
     if (a.px0) { MPC_UNROLL for (int i = 0; i < NX; i++) px0[i] = a.px0[i * a.Bs + b]; }
     if (a.py0) { MPC_UNROLL for (int i = 0; i < NY; i++) py0[i] = a.py0[i * a.Bs + b]; }
-    const int st = target_lane<NX, NU, NY, ND>(P, usp, ysp, dh, usprev, xs, us, ys, it, nullptr, 0, nullptr, a.px0 ? px0 : nullptr, a.py0 ? py0 : nullptr);
+    const int st = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, usprev, xs, us, ys, it, nullptr, 0, nullptr, a.px0 ? px0 : nullptr, a.py0 ? py0 : nullptr);
     a.status[b] = st; a.iters[b] = it;
     MPC_UNROLL for (int i = 0; i < NX; i++) a.xs[i * a.Bs + b] = xs[i];
     MPC_UNROLL for (int i = 0; i < NU; i++) a.us[i * a.Bs + b] = us[i];
@@ -334,7 +337,7 @@ struct LoopArgs {
     int32_t *ws_valid;                               // [Bs] 1 if the workspace holds a solved OCP of the previous step
     int32_t *kf_valid;                               // [Bs] 1 if Kg / Pn hold the filter gain of this step and the prior after it
     double *Kg, *Pn;                                 // [ne*ny][Bs], [ne*ne][Bs] (horizon-parallel kernel: computed one step ahead)
-    double *tw; int32_t *tw_valid;                   // warm start of the target solve: [2*nu + 3*(nx+nu+ny)][Bs], [Bs]
+    double *tw; int32_t *tw_valid;                   // warm start of the target solve: [2*(nu-nh_ss) + 3*(nx+nu+ny+ng_ss)][Bs], [Bs]
     double *ws;
     int B, nsteps; size_t Bs;
     int N;                                           // horizon (host side: sizes the dynamic LDS of the wave-autonomous kernel)
@@ -380,7 +383,7 @@ __device__ __forceinline__ void plant_next(const PT &P, const double (&x)[NXP], 
 #endif
 }
 
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64) void loop_kernel(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
     constexpr int NS = NX + (DU ? NU : 0) + NG, NE = NX + ND;
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(64) void loop_kernel(const DevProblem *__restrict__
         MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
         MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
         int it_ss;
-        const int st_ss = target_lane<NX, NU, NY, ND>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, a.tw + b, Bs, a.tw_valid + b);
+        const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, a.tw + b, Bs, a.tw_valid + b);
         if (st_ss != kInfeasible) {
             MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
             MPC_UNROLL for (int i = 0; i < NU; i++) us[i] = us_n[i];
@@ -501,7 +504,7 @@ __global__ __launch_bounds__(64) void loop_kernel(const DevProblem *__restrict__
 // The closed loop of a problem with SOFT output constraints (slacks = True; mpc_soft.hpp): loop_kernel's step - instance per lane, the same estimator, target and
 // plant code - with the arrowhead solver as its OCP, cold every step like ocp_kernel_soft: a fused run is the loop of the three C-ABI calls per step.  The optimal
 // slacks of every step go to the log SL (MPC_code.py:800).  One instantiation per dimension set.
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64) void loop_kernel_soft(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
     constexpr int NS = NX + (DU ? NU : 0) + NG, NE = NX + ND;
@@ -549,7 +552,7 @@ __global__ __launch_bounds__(64) void loop_kernel_soft(const DevProblem *__restr
         MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
         MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
         int it_ss;
-        const int st_ss = target_lane<NX, NU, NY, ND>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, a.tw + b, Bs, a.tw_valid + b);
+        const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, a.tw + b, Bs, a.tw_valid + b);
         if (st_ss != kInfeasible) {
             MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
             MPC_UNROLL for (int i = 0; i < NU; i++) us[i] = us_n[i];
@@ -665,6 +668,7 @@ __global__ __launch_bounds__(64) void loop_kernel_pxy(const DevProblem *__restri
         MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
         MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
         int it_ss;
+        // (no user rows of the target here: NGS = NHS = 0 by construction - make_launchers_mode instantiates this loop only for sets without them)
         const int st_ss = target_lane<NX, NU, NY, ND>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, nullptr, 0, nullptr, pxh ? px0 : nullptr, pyh ? py0 : nullptr);
         if (st_ss != kInfeasible) {
             MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
@@ -765,14 +769,14 @@ __global__ __launch_bounds__(64) void loop_kernel_pxy(const DevProblem *__restri
 // The closed loop with the horizon-parallel OCP solver (mpc_tp.hpp): a workgroup of NI waves owns NI instances.
 // Wave 0, lane i < NI does for instance i what one lane of loop_kernel does (estimator, target, hold rules, plant);
 // all waves solve the OCPs together.  Between the two halves of a step the loop state lives in HBM.
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NW, int IPW>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NW, int IPW, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64 * NW) void loop_kernel_tp(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
     constexpr int NS = NX + (DU ? NU : 0) + NG, NE = NX + ND;
-    using Cfg = TpCfg<NS, NU, NC, NW, IPW>;
+    using Cfg = TpCfg<NS, NU, NC, NW, IPW, 3 * NGS>;      // (the keep slot grows with the target's inequality rows)
     constexpr int NI = Cfg::NI;
     extern __shared__ double tp_smem[];
-    const TpShared<NS, NU, NC, NW, IPW> sh(tp_smem);
+    const TpShared<NS, NU, NC, NW, IPW, 3 * NGS> sh(tp_smem);
     const DevProblem &P = *Pp;
     const size_t Bs = a.Bs;
     const int lane = threadIdx.x;
@@ -783,7 +787,7 @@ __global__ __launch_bounds__(64 * NW) void loop_kernel_tp(const DevProblem *__re
     double *wsg = a.ws + (size_t)blockIdx.x * NI * Cfg::ROWS_ST * 64;      // state rows of this workgroup's instances
     // the warm start of the target problem lives in LDS for the steps of this launch: a dependent round trip to HBM costs
     // about 12 k cycles while the other workgroups stream their iterates, and the target solve would make three per step
-    constexpr int NTW = 2 * NU + 3 * (NX + NU + NY);
+    constexpr int NTW = 2 * (NU - NHS) + 3 * (NX + NU + NY + NGS);
     static_assert(NTW <= Cfg::KEEP_MAX, "target warm start does not fit its LDS slot");
     double *twk = sh.keep + lane * Cfg::KEEP_MAX;
     if (valid) {
@@ -867,7 +871,7 @@ __global__ __launch_bounds__(64 * NW) void loop_kernel_tp(const DevProblem *__re
             MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
             MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
             int it_ss;
-            const int st_ss = target_lane<NX, NU, NY, ND>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, twk, 1, sh.keepflag + lane);
+            const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, twk, 1, sh.keepflag + lane);
             if (st_ss != kInfeasible) {
                 MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
                 MPC_UNROLL for (int i = 0; i < NU; i++) us[i] = us_n[i];
@@ -981,11 +985,12 @@ __device__ __forceinline__ bool wv_term_aim(int N, double *q, int *iflag, int *a
 // The closed loop on autonomous waves (mpc_wave.hpp): one wave = one workgroup = four instances, for all steps of the launch.
 // Lane i < 4 does for instance i what one lane of loop_kernel does (estimator, target, hold rules, plant) on state kept in LDS;
 // all 64 lanes solve the four OCPs.  HBM sees the state at the first and the last step of a launch and the logs in between.
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS = 0, int NHS = 0>
 struct WvKernelCfg {
     static constexpr int NS = NX + (DU ? NU : 0) + NG, NE = NX + ND, NDD = ND > 0 ? ND : 1;
     using Cfg = WvCfg<NS, NU, NC, NI>;
-    static constexpr int NTW = 2 * NU + 3 * (NX + NU + NY);
+    using RT = Row16Tab<NX, NU, NY, ND, NGS, NHS>;
+    static constexpr int NTW = 2 * (NU - NHS) + 3 * (NX + NU + NY + NGS);
     // per-instance state kept in LDS across the steps of a launch
     static constexpr int K_X = 0, K_XH = NXP, K_DH = K_XH + NX, K_U = K_DH + NDD, K_XS = K_U + NU, K_US = K_XS + NX, K_P = K_US + NU,
                          K_TW = K_P + NE * NE, KEEP = K_TW + NTW;
@@ -994,17 +999,17 @@ struct WvKernelCfg {
     // instance data behind it), so the region is the larger of the two.
     static constexpr int t_region(int N)
     {
-        const int t = Cfg::t_doubles(N), x = Cfg::GUARD + (Row16Tab<NX, NU, NY, ND>::fits ? 4 * Row16Tab<NX, NU, NY, ND>::XCH : 0);
+        const int t = Cfg::t_doubles(N), x = Cfg::GUARD + (RT::fits ? 4 * RT::XCH : 0);
         return t > x ? t : x;
     }
-    static constexpr size_t lds_bytes(int N) { return sizeof(double) * ((size_t)t_region(N) + NI * Cfg::QN + NI * Cfg::OUT + NI * KEEP + (Row16Tab<NX, NU, NY, ND>::fits ? Row16Tab<NX, NU, NY, ND>::DOUBLES : 0)) + sizeof(int) * 24; }
+    static constexpr size_t lds_bytes(int N) { return sizeof(double) * ((size_t)t_region(N) + NI * Cfg::QN + NI * Cfg::OUT + NI * KEEP + (RT::fits ? RT::DOUBLES : 0)) + sizeof(int) * 24; }
     static constexpr int ni() { return NI; }
 };
 
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
-    using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI>;
+    using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
     using Cfg = typename KC::Cfg;
     constexpr int NS = KC::NS, NE = KC::NE, NDD = KC::NDD, NTW = KC::NTW, KEEP = KC::KEEP;
     extern __shared__ double wv_smem[];
@@ -1012,7 +1017,7 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
     const int LD = Cfg::ld(P0.N);
     double *const T = wv_smem + Cfg::GUARD, *const q = wv_smem + KC::t_region(P0.N), *const outv = q + NI * Cfg::QN, *const keep = outv + NI * Cfg::OUT;
     int *const iflag = (int *)(keep + NI * KEEP), *const twv = iflag + 4, *const wsv = twv + 4, *const aimv = wsv + 4, *const itacc = aimv + 4;      // (terminal equality: wv_term_aim)
-    using RT = Row16Tab<NX, NU, NY, ND>;
+    using RT = typename KC::RT;
     double *const tab = (double *)(wsv + 16);      // per-row constants of the 16-lanes-per-instance phases
     // the problem constants are read through the constant address space: immutable by definition, so every access is a scalar
     // load whatever the kernel has stored to global memory in between (as plain global data they turn into vector loads + waits)
@@ -1034,7 +1039,7 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
     } else if (lane < NI) { twv[lane] = 0; wsv[lane] = 0; }
     for (int i = lane; i < NI * LD; i += 64) T[Cfg::RZ * NI * LD + i] = 0.0;      // the zero row of the tile view
     if (lane < Cfg::GUARD) wv_smem[lane] = 0.0;
-    if (RT::fits) row16_fill_tables<NX, NU, NY, ND>(P, tab, lane);
+    if (RT::fits) row16_fill_tables<NX, NU, NY, ND, NGS, NHS>(P, tab, lane);
     __syncthreads();
     // resident iterates: the warm start of a previous launch (inputs and bound multipliers), lane = block
     WvIterA<NS, NU, NC> X[NI];
@@ -1076,7 +1081,7 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
             MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = kq[KC::K_DH + i];
             MPC_UNROLL for (int i = 0; i < NU; i++) usv[i] = kq[KC::K_US + i];
             int it_ss; double vrow;
-            const int st_ss = target_row16<NX, NU, NY, ND>(P, r16, tab, a.usp + k * NU, a.ysp + k * NY, dh, usv, kq + KC::K_TW, twv + b16c, inst16, vrow, it_ss);
+            const int st_ss = target_row16<NX, NU, NY, ND, NGS, NHS>(P, r16, tab, a.usp + k * NU, a.ysp + k * NY, dh, usv, kq + KC::K_TW, twv + b16c, inst16, vrow, it_ss);
             // accept, or keep the previous target when infeasible (MPC_code.py:714-718); rows 0..NX-1 = xs, NX..NX+NU-1 = us
             const bool trow = r16 < NX + NU && b16 < NI;      // lanes of unused instance slots (NI < 4) alias slot 0: they must not write
             const double prev = trow ? kq[KC::K_XS + r16] : 0.0;      // K_XS.. and K_US.. are adjacent
@@ -1136,7 +1141,7 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
                 MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
                 MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
                 int it_ss;
-                const int st_ss = target_lane<NX, NU, NY, ND>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, kp + KC::K_TW, 1, twv + lane);
+                const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, kp + KC::K_TW, 1, twv + lane);
                 if (st_ss != kInfeasible) {
                     MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
                     MPC_UNROLL for (int i = 0; i < NU; i++) us[i] = us_n[i];
@@ -1411,11 +1416,11 @@ static constexpr int kTpMaxBatch = 16384;     // auto choice of the loop kernel 
 // bound modes: which variant of the OCP kernels a problem may use (cheapest first)
 enum { kBoundsAllFinite = 1, kBoundsInputsOnly = 2, kBoundsGeneric = 0 };
 
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS, int NHS>
 static int launch_loop_wv(const DevProblem *p, LoopArgs a, hipStream_t s, int dev)
 {
-    using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI>;
-    auto kern = loop_kernel_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI>;
+    using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
+    auto kern = loop_kernel_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
     static bool attr_set[64] = {};      // per device: more than 64 KB of dynamic LDS has to be asked for
     if (!attr_set[dev]) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KC::lds_bytes(64)) != hipSuccess) return -1;
@@ -1425,7 +1430,7 @@ static int launch_loop_wv(const DevProblem *p, LoopArgs a, hipStream_t s, int de
     return 0;
 }
 
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NGS, int NHS>
 static Launchers make_launchers_mode()
 {
     Launchers l;
@@ -1433,21 +1438,26 @@ static Launchers make_launchers_mode()
     {
         constexpr int NSZ = NX + (DU ? NU : 0) + NG;
         l.ocp_pxy = [](const DevProblem *p, OcpPxyArgs a, hipStream_t s) { hipLaunchKernelGGL((ocp_kernel_pxy<NX, NU, NY, ND, DU, NG>), dim3((a.o.B + 63) / 64), dim3(64), 0, s, p, a); };
-        l.loop_pxy = [](const DevProblem *p, LoopArgs a, hipStream_t s) { hipLaunchKernelGGL((loop_kernel_pxy<NX, NU, NY, ND, NXP, DU, NG>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
+        // (loop_kernel_pxy solves its target without user rows - their constant would need p_y_0: a set with rows has no such loop, and
+        // mpc_loop_set_model_schedule refuses it before this pointer is ever needed)
+        if constexpr (NGS == 0 && NHS == 0)
+            l.loop_pxy = [](const DevProblem *p, LoopArgs a, hipStream_t s) { hipLaunchKernelGGL((loop_kernel_pxy<NX, NU, NY, ND, NXP, DU, NG>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
+        else
+            l.loop_pxy = nullptr;
         l.pxy_ws_rows = 2 * BlkLayout<NSZ, NU, NSZ + NU>::SLOTS; l.pxy_nc = NSZ + NU; l.pxy_lin = NSZ * (NSZ + NU + 1) + 2 * NSZ;
         l.ocp_soft = [](const DevProblem *p, OcpSoftArgs a, hipStream_t s) { hipLaunchKernelGGL((ocp_kernel_soft<NX, NU, NY, ND, DU, NG>), dim3((a.o.B + 63) / 64), dim3(64), 0, s, p, a); };
         l.soft_fields = SoftLayout<NSZ, NU, NY>::FIELDS;
-        l.loop_soft = [](const DevProblem *p, LoopArgs a, hipStream_t s) { hipLaunchKernelGGL((loop_kernel_soft<NX, NU, NY, ND, NXP, DU, NG>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
+        l.loop_soft = [](const DevProblem *p, LoopArgs a, hipStream_t s) { hipLaunchKernelGGL((loop_kernel_soft<NX, NU, NY, ND, NXP, DU, NG, NGS, NHS>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
     }
-    l.target = [](const DevProblem *p, TargetArgs a, hipStream_t s) { hipLaunchKernelGGL((target_kernel<NX, NU, NY, ND>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
+    l.target = [](const DevProblem *p, TargetArgs a, hipStream_t s) { hipLaunchKernelGGL((target_kernel<NX, NU, NY, ND, NGS, NHS>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
     l.kf = [](const DevProblem *p, KfArgs a, hipStream_t s) { hipLaunchKernelGGL((kf_kernel<NX, NY, ND>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
-    l.loop = [](const DevProblem *p, LoopArgs a, hipStream_t s) { hipLaunchKernelGGL((loop_kernel<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
+    l.loop = [](const DevProblem *p, LoopArgs a, hipStream_t s) { hipLaunchKernelGGL((loop_kernel<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NGS, NHS>), dim3((a.B + 63) / 64), dim3(64), 0, s, p, a); };
     l.ws_rows = 2 * BlkLayout<NX + (DU ? NU : 0) + NG, NU, NC>::SLOTS;   // doubles per instance per block
     {
         // eight waves (256 VGPRs each); two instances per wave when their transposing buffer still fits the 160 KB of LDS
         constexpr int NW = 8, NSZ = NX + (DU ? NU : 0) + NG;
-        constexpr int IPW = TpCfg<NSZ, NU, NC, NW, 2>::lds_bytes() <= 160 * 1024 ? 2 : 1;
-        using Cfg = TpCfg<NSZ, NU, NC, NW, IPW>;
+        constexpr int IPW = TpCfg<NSZ, NU, NC, NW, 2, 3 * NGS>::lds_bytes() <= 160 * 1024 ? 2 : 1;
+        using Cfg = TpCfg<NSZ, NU, NC, NW, IPW, 3 * NGS>;
         constexpr size_t lds = Cfg::lds_bytes();
         l.tp_ni = Cfg::NI; l.tp_lds = lds; l.tp_ws_per_inst = sizeof(double) * 64 * Cfg::ROWS_ST; l.tp_ws_per_group = 0;
         l.loop_tp = nullptr;
@@ -1456,7 +1466,7 @@ static Launchers make_launchers_mode()
         l.tp_max_batch = (NSZ <= 4 && NU <= 2) ? INT32_MAX : kTpMaxBatch;
         if (lds <= 160 * 1024) {
             l.loop_tp = [](const DevProblem *p, LoopArgs a, hipStream_t s) -> int {
-                auto kern = loop_kernel_tp<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NW, IPW>;
+                auto kern = loop_kernel_tp<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NW, IPW, NGS, NHS>;
                 static bool attr_set[64] = {};      // per device: more than 64 KB of dynamic LDS has to be asked for
                 int dev = 0;
                 if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
@@ -1475,7 +1485,7 @@ static Launchers make_launchers_mode()
         // registers they are parked in (4 NC slacks / multipliers + NV primal + NC predictor direction, two registers each), else two
         constexpr int NSZ_ = NX + (DU ? NU : 0) + NG;
         constexpr int NI = (5 * NC + NSZ_ + NU) * 2 * 4 <= 248 ? 4 : 2;
-        using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI>;
+        using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
         constexpr size_t lds = KC::lds_bytes(64);      // the longest horizon; a launch asks for what its own horizon needs
         l.wv_lds = lds; l.wv_ws_per_inst = sizeof(double) * 64 * KC::Cfg::ROWS_WS;
         if (lds <= 160 * 1024) {
@@ -1499,10 +1509,10 @@ static Launchers make_launchers_mode()
                 constexpr bool small = true;
 #endif
                 if constexpr (small) {
-                    if (ni == 1) return launch_loop_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, 1>(p, a, s, dev);
-                    if (ni == 2) return launch_loop_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, 2>(p, a, s, dev);
+                    if (ni == 1) return launch_loop_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, 1, NGS, NHS>(p, a, s, dev);
+                    if (ni == 2) return launch_loop_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, 2, NGS, NHS>(p, a, s, dev);
                 }
-                return launch_loop_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI>(p, a, s, dev);
+                return launch_loop_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>(p, a, s, dev);
             };
             l.wv_ns = NSZ_;
             l.ocp_wv = [](const DevProblem *p, OcpWvArgs a, int N, hipStream_t s) -> int {
@@ -1525,32 +1535,34 @@ static Launchers make_launchers_mode()
     return l;
 }
 
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG>
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NGS, int NHS>
 static Launchers make_launchers(int mode)
 {
     constexpr int NS = NX + (DU ? NU : 0) + NG;
-    if (NG == 0 && mode == kBoundsAllFinite) return make_launchers_mode<NX, NU, NY, ND, NXP, DU, NG, NS + NU, false>();
-    if (NG == 0 && mode == kBoundsInputsOnly) return make_launchers_mode<NX, NU, NY, ND, NXP, DU, NG, NU, false>();
-    return make_launchers_mode<NX, NU, NY, ND, NXP, DU, NG, NS + NU, true>();      // output-row states are free at the terminal stage: masks
+    if (NG == 0 && mode == kBoundsAllFinite) return make_launchers_mode<NX, NU, NY, ND, NXP, DU, NG, NS + NU, false, NGS, NHS>();
+    if (NG == 0 && mode == kBoundsInputsOnly) return make_launchers_mode<NX, NU, NY, ND, NXP, DU, NG, NU, false, NGS, NHS>();
+    return make_launchers_mode<NX, NU, NY, ND, NXP, DU, NG, NS + NU, true, NGS, NHS>();      // output-row states are free at the terminal stage: masks
 }
 
 #ifdef MPC_PART2
 // second object of the default library: nothing but the kernels of its dimension sets
-extern "C" int mpc_part2_launchers(int nx, int nu, int ny, int nd, int nxp, int du, int ng, int mode, void *out)
+extern "C" int mpc_part2_launchers(int nx, int nu, int ny, int nd, int nxp, int du, int ng, int ngs, int nhs, int mode, void *out)
 {
     bool found = false;
-#define MPC_TRY_DIM(NX, NU, NY, ND, NXP, DU, NG)                                                              \
-    if (!found && nx == NX && nu == NU && ny == NY && nd == ND && nxp == NXP && (du != 0) == (DU != 0) && ng == NG) { \
-        *(Launchers *)out = make_launchers<NX, NU, NY, ND, NXP, (DU != 0), NG>(mode);                          \
+#define MPC_TRY_DIM9(NX, NU, NY, ND, NXP, DU, NG, NGS, NHS)                                                   \
+    if (!found && nx == NX && nu == NU && ny == NY && nd == ND && nxp == NXP && (du != 0) == (DU != 0) && ng == NG && ngs == NGS && nhs == NHS) { \
+        *(Launchers *)out = make_launchers<NX, NU, NY, ND, NXP, (DU != 0), NG, NGS, NHS>(mode);                \
         found = true;                                                                                         \
     }
+#define MPC_TRY_DIM(...) MPC_DIM9(MPC_TRY_DIM9, __VA_ARGS__)
     MPC_DIM_LIST(MPC_TRY_DIM)
 #undef MPC_TRY_DIM
+#undef MPC_TRY_DIM9
     return found ? 1 : 0;
 }
 #else
 #ifdef MPC_HAVE_PART2
-extern "C" int mpc_part2_launchers(int nx, int nu, int ny, int nd, int nxp, int du, int ng, int mode, void *out);
+extern "C" int mpc_part2_launchers(int nx, int nu, int ny, int nd, int nxp, int du, int ng, int ngs, int nhs, int mode, void *out);
 #endif
 
 struct DevBuf {
@@ -1635,17 +1647,24 @@ static int general_output_rows(const mpc_lin_desc *d, int *rows)
     return ng;
 }
 
-// Householder QR of [A-I, B]' and the reduced target problem
+// Householder QR of [A-I, B; Hx_ss, Hu_ss]' and the reduced target problem (DESIGN.md sections 4.5, 15).  The equality rows of the target
+// (User_h_eq_SS) join the steady-state rows: the particular solution maps [cx; ch] (Ep | Eh), the null space keeps nu - nh_ss columns.
+// The inequality rows (User_g_ineq_SS) are rows nx+nu+ny.. of W (Wg = Gv_ss Zn) with the bounds (-inf, 0] and the per-instance constant
+// Gv_ss vp + Gd_ss dhat + g0_ss in w0 (mpc_device.hpp:target_lane).  Without rows this is the reduction of [A-I, B]' alone, operation for operation.
 static int build_target(const mpc_lin_desc *d, DevProblem &P)
 {
-    const int n = d->nx, m = d->nu, q = d->ny, nv = n + m;
-    double Qf[kMaxV][kMaxV], Rm[kMaxV][kMaxN];
+    const int n = d->nx, m = d->nu, q = d->ny, nv = n + m, nh = d->n_ss_eq_rows, nk = n + nh, mr = m - nh;
+    double Qf[kMaxV][kMaxV], Rm[kMaxV][kMaxV];
     for (int i = 0; i < nv; i++) for (int j = 0; j < nv; j++) Qf[i][j] = (i == j) ? 1.0 : 0.0;
     for (int i = 0; i < n; i++) {
         for (int j = 0; j < n; j++) Rm[j][i] = d->A[i * n + j] - (i == j ? 1.0 : 0.0);
         for (int j = 0; j < m; j++) Rm[n + j][i] = d->B[i * m + j];
     }
-    for (int k = 0; k < n; k++) {
+    for (int i = 0; i < nh; i++) {
+        for (int j = 0; j < n; j++) Rm[j][n + i] = d->Hx_ss[i * n + j];
+        for (int j = 0; j < m; j++) Rm[n + j][n + i] = d->Hu_ss[i * m + j];
+    }
+    for (int k = 0; k < nk; k++) {
         double v[kMaxV], nrm = 0.0, vn = 0.0;
         for (int i = k; i < nv; i++) nrm += Rm[i][k] * Rm[i][k];
         nrm = std::sqrt(nrm);
@@ -1655,42 +1674,58 @@ static int build_target(const mpc_lin_desc *d, DevProblem &P)
         v[k] -= alpha;
         for (int i = k; i < nv; i++) vn += v[i] * v[i];
         if (vn > 0.0) {
-            for (int j = 0; j < n; j++) { double s = 0.0; for (int i = k; i < nv; i++) s += v[i] * Rm[i][j]; s *= 2.0 / vn; for (int i = k; i < nv; i++) Rm[i][j] -= s * v[i]; }
+            for (int j = 0; j < nk; j++) { double s = 0.0; for (int i = k; i < nv; i++) s += v[i] * Rm[i][j]; s *= 2.0 / vn; for (int i = k; i < nv; i++) Rm[i][j] -= s * v[i]; }
             for (int j = 0; j < nv; j++) { double s = 0.0; for (int i = k; i < nv; i++) s += Qf[j][i] * v[i]; s *= 2.0 / vn; for (int i = k; i < nv; i++) Qf[j][i] -= s * v[i]; }
         }
     }
     double rmax = 0.0;
-    for (int k = 0; k < n; k++) rmax = std::fmax(rmax, std::fabs(Rm[k][k]));
-    for (int k = 0; k < n; k++) if (std::fabs(Rm[k][k]) < 1e-12 * rmax) return -1;
-    double Rti[kMaxN][kMaxN];
-    for (int c = 0; c < n; c++)
-        for (int i = 0; i < n; i++) {
+    for (int k = 0; k < nk; k++) rmax = std::fmax(rmax, std::fabs(Rm[k][k]));
+    for (int k = 0; k < nk; k++) if (std::fabs(Rm[k][k]) < 1e-12 * rmax) return -1;
+    double Rti[kMaxV][kMaxV];
+    for (int c = 0; c < nk; c++)
+        for (int i = 0; i < nk; i++) {
             double s = (i == c) ? 1.0 : 0.0;
             for (int j = 0; j < i; j++) s -= Rm[j][i] * Rti[j][c];
             Rti[i][c] = s / Rm[i][i];
         }
-    for (int r = 0; r < nv; r++) for (int c = 0; c < n; c++) { double s = 0.0; for (int j = 0; j < n; j++) s += Qf[r][j] * Rti[j][c]; P.Ep[r][c] = s; }
-    for (int r = 0; r < nv; r++) for (int c = 0; c < m; c++) P.Zn[r][c] = Qf[r][n + c];
-    for (int i = 0; i < q; i++) for (int c = 0; c < m; c++) { double s = 0.0; for (int j = 0; j < n; j++) s += d->C[i * n + j] * P.Zn[j][c]; P.CZx[i][c] = s; }
-    for (int a = 0; a < m; a++) for (int b = 0; b < m; b++) {
+    for (int r = 0; r < nv; r++) for (int c = 0; c < nk; c++) {
+        double s = 0.0;
+        for (int j = 0; j < nk; j++) s += Qf[r][j] * Rti[j][c];
+        if (c < n) P.Ep[r][c] = s; else P.Eh[r][c - n] = s;
+    }
+    for (int r = 0; r < nv; r++) for (int c = 0; c < mr; c++) P.Zn[r][c] = Qf[r][nk + c];
+    for (int i = 0; i < q; i++) for (int c = 0; c < mr; c++) { double s = 0.0; for (int j = 0; j < n; j++) s += d->C[i * n + j] * P.Zn[j][c]; P.CZx[i][c] = s; }
+    for (int a = 0; a < mr; a++) for (int b = 0; b < mr; b++) {
         double s = 0.0;
         for (int i = 0; i < q; i++) for (int j = 0; j < q; j++) s += P.CZx[i][a] * d->Qss[i * q + j] * P.CZx[j][b];
         for (int i = 0; i < m; i++) for (int j = 0; j < m; j++) s += P.Zn[n + i][a] * d->Rss[i * m + j] * P.Zn[n + j][b];
         P.Hr[a][b] = s;
     }
-    for (int a = 0; a < m; a++) for (int b = 0; b < a; b++) { const double s = 0.5 * (P.Hr[a][b] + P.Hr[b][a]); P.Hr[a][b] = P.Hr[b][a] = s; }
-    for (int r = 0; r < nv; r++) for (int c = 0; c < m; c++) P.W[r][c] = P.Zn[r][c];
-    for (int r = 0; r < q; r++) for (int c = 0; c < m; c++) P.W[nv + r][c] = P.CZx[r][c];
+    for (int a = 0; a < mr; a++) for (int b = 0; b < a; b++) { const double s = 0.5 * (P.Hr[a][b] + P.Hr[b][a]); P.Hr[a][b] = P.Hr[b][a] = s; }
+    for (int r = 0; r < nv; r++) for (int c = 0; c < mr; c++) P.W[r][c] = P.Zn[r][c];
+    for (int r = 0; r < q; r++) for (int c = 0; c < mr; c++) P.W[nv + r][c] = P.CZx[r][c];
     for (int i = 0; i < n; i++) { P.tlo[i] = d->xmin_ss[i]; P.thi[i] = d->xmax_ss[i]; }
     for (int i = 0; i < m; i++) { P.tlo[n + i] = d->umin_ss[i]; P.thi[n + i] = d->umax_ss[i]; }
     for (int i = 0; i < q; i++) { P.tlo[nv + i] = d->ymin_ss[i]; P.thi[nv + i] = d->ymax_ss[i]; }
     for (int i = 0; i < q; i++) for (int j = 0; j < q; j++) P.Qss[i][j] = d->Qss[i * q + j];
     for (int i = 0; i < m; i++) for (int j = 0; j < m; j++) P.Rss[i][j] = d->Rss[i * m + j];
+    P.ng_ss = d->n_ss_ineq_rows; P.nh_ss = nh;
+    for (int h = 0; h < nh; h++) {
+        for (int j = 0; j < d->nd; j++) P.Hd_ss[h][j] = d->Hd_ss[h * d->nd + j];
+        P.h0_ss[h] = d->h0_ss[h];
+    }
+    for (int g = 0; g < P.ng_ss; g++) {
+        for (int j = 0; j < n; j++) P.Gv_ss[g][j] = d->Gx_ss[g * n + j];
+        for (int j = 0; j < m; j++) P.Gv_ss[g][n + j] = d->Gu_ss[g * m + j];
+        for (int j = 0; j < d->nd; j++) P.Gd_ss[g][j] = d->Gd_ss[g * d->nd + j];
+        P.g0_ss[g] = d->g0_ss[g];
+        for (int c = 0; c < mr; c++) { double s = 0.0; for (int j = 0; j < nv; j++) s += P.Gv_ss[g][j] * P.Zn[j][c]; P.Wg[g][c] = s; }
+    }
     // the reduced Hessian must be positive definite (unique target)
-    if (m == 1) { if (!(P.Hr[0][0] > 0)) return -2; }
+    if (mr == 1) { if (!(P.Hr[0][0] > 0)) return -2; }
     else {
         double c[kMaxM][kMaxM];
-        for (int i = 0; i < m; i++) for (int j = 0; j <= i; j++) {
+        for (int i = 0; i < mr; i++) for (int j = 0; j <= i; j++) {
             double a = P.Hr[i][j];
             for (int k = 0; k < j; k++) a -= c[i][k] * c[j][k];
             if (i == j) { if (!(a > 0)) return -2; c[i][i] = std::sqrt(a); } else c[i][j] = a / c[j][j];
@@ -1824,8 +1859,13 @@ static int build_problem(const mpc_lin_desc *d, DevProblem &P)
         if (!d->K) return fail(-3, "MPC_EST_FIXED_GAIN needs K");
         for (int i = 0; i < ne; i++) for (int j = 0; j < q; j++) P.Kfix[i][j] = d->K[i * q + j];
     }
+    if (d->n_ss_ineq_rows && (!d->Gx_ss || !d->Gu_ss || !d->g0_ss || (nd > 0 && !d->Gd_ss)))
+        return fail(-1, "n_ss_ineq_rows = %d needs Gx_ss, Gu_ss, Gd_ss, g0_ss", d->n_ss_ineq_rows);
+    if (d->n_ss_eq_rows && (!d->Hx_ss || !d->Hu_ss || !d->h0_ss || (nd > 0 && !d->Hd_ss)))
+        return fail(-1, "n_ss_eq_rows = %d needs Hx_ss, Hu_ss, Hd_ss, h0_ss", d->n_ss_eq_rows);
     const int rc = build_target(d, P);
-    if (rc == -1) return fail(-4, "[A-I, B] is rank deficient: no steady state for arbitrary disturbances");
+    if (rc == -1) return fail(-4, d->n_ss_eq_rows ? "[A-I, B; Hx_ss, Hu_ss] is rank deficient: the target's equality rows depend on each other or on the steady-state rows"
+                                                  : "[A-I, B] is rank deficient: no steady state for arbitrary disturbances");
     if (rc == -2) return fail(-4, "reduced Hessian of the target problem is not positive definite");
     return 0;
 }
@@ -1854,25 +1894,29 @@ extern "C" int mpc_lin_create(const mpc_lin_desc *d, mpc_handle **out)
     const int ns = d->nx + (stage_has_uprev(d) ? d->nu : 0) + general_output_rows(d, nullptr);
     if (d->nx < 1 || d->nu < 1 || ns > kMaxN || d->nu > kMaxM || d->ny > kMaxY || d->nd > kMaxD || d->nxp > kMaxN || d->N < 2 || d->N > 512)
         return fail(-2, "dimensions out of range (stage state <= %d, nu <= %d, ny <= %d, nd <= %d, 2 <= N <= 512)", kMaxN, kMaxM, kMaxY, kMaxD);
+    if (d->n_ss_ineq_rows < 0 || d->n_ss_ineq_rows > kMaxGS || d->n_ss_eq_rows < 0 || d->n_ss_eq_rows >= d->nu)
+        return fail(-2, "target rows out of range (0 <= n_ss_ineq_rows <= %d, 0 <= n_ss_eq_rows < nu: the target keeps a free direction)", kMaxGS);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(-11, "no HIP device: the MI355X path is required (there is no CPU fallback)");
     if (d->device < 0 || d->device >= ndev) return fail(-11, "device %d out of range (have %d)", d->device, ndev);
     mpc_handle *h = new mpc_handle();
     bool found = false;
-    const int ng = general_output_rows(d, nullptr);
-#define MPC_TRY_DIM(NX, NU, NY, ND, NXP, DU, NG)                                                              \
-    if (!found && d->nx == NX && d->nu == NU && d->ny == NY && d->nd == ND && d->nxp == NXP && stage_has_uprev(d) == (DU != 0) && ng == NG) { \
-        h->L = make_launchers<NX, NU, NY, ND, NXP, (DU != 0), NG>(bound_mode(d));                             \
+    const int ng = general_output_rows(d, nullptr), ngs = d->n_ss_ineq_rows, nhs = d->n_ss_eq_rows;
+#define MPC_TRY_DIM9(NX, NU, NY, ND, NXP, DU, NG, NGS, NHS)                                                   \
+    if (!found && d->nx == NX && d->nu == NU && d->ny == NY && d->nd == ND && d->nxp == NXP && stage_has_uprev(d) == (DU != 0) && ng == NG && ngs == NGS && nhs == NHS) { \
+        h->L = make_launchers<NX, NU, NY, ND, NXP, (DU != 0), NG, NGS, NHS>(bound_mode(d));                   \
         found = true;                                                                                         \
     }
+#define MPC_TRY_DIM(...) MPC_DIM9(MPC_TRY_DIM9, __VA_ARGS__)
     MPC_DIM_LIST(MPC_TRY_DIM)
 #undef MPC_TRY_DIM
+#undef MPC_TRY_DIM9
 #ifdef MPC_HAVE_PART2
-    if (!found) found = mpc_part2_launchers(d->nx, d->nu, d->ny, d->nd, d->nxp, stage_has_uprev(d) ? 1 : 0, ng, bound_mode(d), &h->L) != 0;
+    if (!found) found = mpc_part2_launchers(d->nx, d->nu, d->ny, d->nd, d->nxp, stage_has_uprev(d) ? 1 : 0, ng, ngs, nhs, bound_mode(d), &h->L) != 0;
 #endif
     if (!found) {
         delete h;
-        return fail(-5, "no kernel compiled for nx=%d nu=%d ny=%d nd=%d nxp=%d du_form=%d general_output_rows=%d (build info: %s)", d->nx, d->nu, d->ny, d->nd, d->nxp, (int)stage_has_uprev(d), ng, mpc_build_info());
+        return fail(-5, "no kernel compiled for nx=%d nu=%d ny=%d nd=%d nxp=%d du_form=%d general_output_rows=%d ss_ineq_rows=%d ss_eq_rows=%d (build info: %s)", d->nx, d->nu, d->ny, d->nd, d->nxp, (int)stage_has_uprev(d), ng, ngs, nhs, mpc_build_info());
     }
 #ifdef MPC_NL_PLANT_HEADER
     if (!d->nl_plant) { delete h; return fail(-5, "this library simulates a user plant (User_fxp_Cont): the descriptor has nl_plant = 0"); }
@@ -1923,13 +1967,15 @@ extern "C" const char *mpc_build_info(void)
 {
     static std::string s;
     if (s.empty()) {
-        s = "gfx950;loop_kernels=wave-autonomous(N<=64&ns<=8&nu<=2),horizon-parallel(N<=64;mfma-riccati:ns<=4&nu<=2,else-batch<=16384),instance-per-lane;dims(nx/nu/ny/nd/nxp/du/ng)=";
-#define MPC_INFO_DIM(NX, NU, NY, ND, NXP, DU, NG) s += #NX "/" #NU "/" #NY "/" #ND "/" #NXP "/" #DU "/" #NG ",";
+        s = "gfx950;loop_kernels=wave-autonomous(N<=64&ns<=8&nu<=2),horizon-parallel(N<=64;mfma-riccati:ns<=4&nu<=2,else-batch<=16384),instance-per-lane;dims(nx/nu/ny/nd/nxp/du/ng[/ngs/nhs])=";
+#define MPC_INFO_DIM9(NX, NU, NY, ND, NXP, DU, NG, NGS, NHS) { s += #NX "/" #NU "/" #NY "/" #ND "/" #NXP "/" #DU "/" #NG; if (NGS || NHS) s += "/" #NGS "/" #NHS; s += ","; }
+#define MPC_INFO_DIM(...) MPC_DIM9(MPC_INFO_DIM9, __VA_ARGS__)
         MPC_DIM_LIST(MPC_INFO_DIM)
 #ifdef MPC_HAVE_PART2
         MPC_DIM_LIST_B(MPC_INFO_DIM)
 #endif
 #undef MPC_INFO_DIM
+#undef MPC_INFO_DIM9
         s.pop_back();
 #ifdef MPC_NL_PLANT_HEADER
         s += ";nlplant";
@@ -2253,6 +2299,7 @@ extern "C" int mpc_set_model_offsets(mpc_handle *h, int32_t B, const double *px0
 {
     if (!h || B < 1) return fail(-1, "bad argument");
     const DevProblem &P = h->hp;
+    if ((px0 || py0) && (P.ng_ss || P.nh_ss)) return fail(-8, "model offsets together with user rows of the target are not carried (the rows' constant would depend on p_y_0)");
     HIP_TRY(hipSetDevice(h->device));
     const size_t Bs = pad64(B);
     h->off_has_px = h->off_has_py = false; h->off_B = B;
@@ -2321,7 +2368,7 @@ extern "C" int mpc_loop_alloc(mpc_handle *h, int32_t B, int32_t max_steps, int32
         h->st_P.ensure((size_t)ne * ne * Bs * 8) || h->st_u.ensure((size_t)P.nu * Bs * 8) || h->st_xs.ensure((size_t)P.nx * Bs * 8) ||
         h->st_us.ensure((size_t)P.nu * Bs * 8) || h->st_flag.ensure(3 * Bs * 4) ||
         h->st_Kg.ensure((size_t)ne * P.ny * Bs * 8) || h->st_Pn.ensure((size_t)ne * ne * Bs * 8) ||
-        h->st_tw.ensure((size_t)(2 * P.nu + 3 * (P.nx + P.nu + P.ny)) * Bs * 8))
+        h->st_tw.ensure((size_t)(2 * (P.nu - P.nh_ss) + 3 * (P.nx + P.nu + P.ny + P.ng_ss)) * Bs * 8))
         return -10;
     // [0,Bs): OCP warm start valid, [Bs,2Bs): filter look-ahead valid, [2Bs,3Bs): target warm start valid.  All resident state is
     // cleared on the handle's (non-blocking) stream: nothing a kernel reads is ever uninitialised, whatever the caller sets later
@@ -2442,6 +2489,7 @@ extern "C" int mpc_loop_set_model_schedule(mpc_handle *h, int32_t nsteps, const 
 {
     if (!h || h->B == 0) return fail(-1, "mpc_loop_alloc first");
     if (!px && !py) { h->msch_steps = 0; h->msch_px = h->msch_py = false; return 0; }
+    if (h->hp.ng_ss || h->hp.nh_ss) return fail(-8, "def_px / def_py together with user rows of the target are not carried (the rows' constant would depend on p_y_0)");
     if (nsteps < 1 || nsteps > h->max_steps) return fail(-1, "nsteps %d exceeds the allocated %d", nsteps, h->max_steps);
     HIP_TRY(hipSetDevice(h->device));
     const DevProblem &P = h->hp;
@@ -2480,6 +2528,7 @@ extern "C" int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps)
     const size_t Bs = h->Bs, ms = h->max_steps;
     const double *sch = (const double *)h->sch.p;
     const bool pxy = h->msch_steps > 0;      // def_px / def_py schedules: the instance-per-lane loop with per-block stage data
+    if (pxy && !h->L.loop_pxy) return fail(-8, "def_px / def_py together with user rows of the target are not carried");
     if (pxy && k0 + nsteps > h->msch_steps) return fail(-1, "steps [%d,%d) outside the model-parameter schedule of %d steps", k0, k0 + nsteps, h->msch_steps);
     if (pxy) {
         const size_t N = P.N;

@@ -38,7 +38,7 @@ constexpr double kWsSMinLo = 1e-9, kWsSMinHi = 1e-6;
 constexpr double kWsMuFactor = 1e4;   // ... minimum complementarity product = kWsMuFactor * (minimum slack)^2
 
 constexpr int kMaxN = 8, kMaxM = 4, kMaxY = 8, kMaxD = 8, kMaxV = kMaxN + kMaxM, kMaxC = kMaxN + kMaxM + kMaxY,
-              kMaxE = kMaxN + kMaxD;
+              kMaxE = kMaxN + kMaxD, kMaxGS = 4;
 
 enum : int { kSolved = 0, kMaxIter = 1, kInfeasible = 2 };
 
@@ -70,6 +70,13 @@ struct DevProblem {
     // widened by one shared slack vector [sl_ub; sl_lb] with weight Ws in every stage's cost - mpc_soft.hpp
     int soft;
     double Ws[2 * kMaxY][2 * kMaxY];
+    // affine user rows of the target problem (User_g_ineq_SS / User_h_eq_SS, Target_Calc.py:87-110,139-155).  Last in the
+    // struct: the offsets of everything above, and so the code of the kernels without these rows, stay what they were.
+    int ng_ss, nh_ss;
+    double Eh[kMaxV][kMaxM];                                         // particular solution vp = -Ep cx - Eh ch, ch = h0_ss + Hd_ss dhat
+    double Hd_ss[kMaxM][kMaxD], h0_ss[kMaxM];
+    double Gv_ss[kMaxGS][kMaxV], Gd_ss[kMaxGS][kMaxD], g0_ss[kMaxGS]; // inequality rows on v = [xs; us] (ys substituted)
+    double Wg[kMaxGS][kMaxM];                                        // ... their rows of W: Gv_ss Zn
 };
 
 typedef __attribute__((address_space(4))) DevProblem ConstProblem;
@@ -797,12 +804,23 @@ __device__ __forceinline__ bool term_aim(const DevProblem &P, const Ws &ws, OcpI
 // --------------------------------------------------------------------------------------------------------
 // tw / twv: warm-start data of the closed loop for this instance, element f at tw[f * tws]: y[NR] l_lo[NC] l_hi[NC] gr[NR] w0[NC]
 // of the last successful solve, and its validity flag; nullptr = cold (the per-call entry point).  DESIGN.md section 4.8.
-template <int NX, int NU, int NY, int ND, class PT>
+// NGS / NHS: affine user rows of the target (User_g_ineq_SS / User_h_eq_SS): the NHS equality rows join [A-I, B] in
+// the null-space reduction (NR = NU - NHS reduced coordinates), the NGS inequality rows are rows NX+NU+NY.. of W with the bounds (-inf, 0].
+// With NGS = NHS = 0 (every caller without such rows, the non-linear path's TargetLocal included) none of their fields is read.
+template <int NVY, int NGS, class PT>
+__device__ __forceinline__ double target_w(const PT &P, int r, int c)
+{
+    if constexpr (NGS > 0) { if (r >= NVY) return P.Wg[r >= NVY ? r - NVY : 0][c]; }
+    return P.W[r < NVY ? r : 0][c];
+}
+
+template <int NX, int NU, int NY, int ND, int NGS = 0, int NHS = 0, class PT>
 __device__ int target_lane(const PT &P, const double *usp, const double *ysp, const double *dhat,
                            const double (&us_prev)[NU], double (&xs)[NX], double (&us)[NU], double (&ys)[NY], int &iters,
                            double *tw = nullptr, size_t tws = 0, int32_t *twv = nullptr, const double *px0 = nullptr, const double *py0 = nullptr)
 {
-    constexpr int NV = NX + NU, NC = NV + NY, NR = NU;
+    static_assert(NGS >= 0 && NGS <= kMaxGS && NHS >= 0 && NHS < NU, "target rows out of range");
+    constexpr int NV = NX + NU, NVY = NV + NY, NC = NVY + NGS, NR = NU - NHS;
     double cx[NX], e[NY], vp[NV], yp[NY], gr[NR], w0[NC], y[NR];
     double s_lo[NC], s_hi[NC], l_lo[NC], l_hi[NC], lo[NC], hi[NC];
     bool fl[NC], fh[NC];
@@ -810,6 +828,11 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
     MPC_UNROLL for (int i = 0; i < NX; i++) { double a = P.fxc[i] + (px0 ? px0[i] : 0.0); MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Bd[i][j] * dhat[j]; cx[i] = a; }
     MPC_UNROLL for (int i = 0; i < NY; i++) { double a = P.fyc[i] + (py0 ? py0[i] : 0.0); MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Cd[i][j] * dhat[j]; e[i] = a; }
     MPC_UNROLL for (int r = 0; r < NV; r++) { double a = 0.0; MPC_UNROLL for (int j = 0; j < NX; j++) a -= P.Ep[r][j] * cx[j]; vp[r] = a; }
+    if constexpr (NHS > 0) {      // the equality rows' right-hand side ch = h0_ss + Hd_ss dhat
+        double ch[NHS];
+        MPC_UNROLL for (int h = 0; h < NHS; h++) { double a = P.h0_ss[h]; MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Hd_ss[h][j] * dhat[j]; ch[h] = a; }
+        MPC_UNROLL for (int r = 0; r < NV; r++) { double a = vp[r]; MPC_UNROLL for (int h = 0; h < NHS; h++) a -= P.Eh[r][h] * ch[h]; vp[r] = a; }
+    }
     MPC_UNROLL for (int i = 0; i < NY; i++) { double a = e[i]; MPC_UNROLL for (int j = 0; j < NX; j++) a += P.Cm[i][j] * vp[j]; yp[i] = a; }
     MPC_UNROLL for (int c = 0; c < NR; c++) {
         double a = 0.0;
@@ -823,9 +846,18 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
     }
     MPC_UNROLL for (int r = 0; r < NV; r++) w0[r] = vp[r];
     MPC_UNROLL for (int r = 0; r < NY; r++) w0[NV + r] = yp[r];
+    if constexpr (NGS > 0) {      // the inequality rows at the particular solution: Gv_ss vp + Gd_ss dhat + g0_ss
+        MPC_UNROLL for (int g = 0; g < NGS; g++) {
+            double a = P.g0_ss[g];
+            MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Gd_ss[g][j] * dhat[j];
+            MPC_UNROLL for (int j = 0; j < NV; j++) a += P.Gv_ss[g][j] * vp[j];
+            w0[NVY + g] = a;
+        }
+    }
     double ncon = 0.0;
     MPC_UNROLL for (int r = 0; r < NC; r++) {
-        fl[r] = fin(P.tlo[r]); fh[r] = fin(P.thi[r]); lo[r] = fl[r] ? P.tlo[r] : 0.0; hi[r] = fh[r] ? P.thi[r] : 0.0;
+        if (r < NVY) { fl[r] = fin(P.tlo[r < NVY ? r : 0]); fh[r] = fin(P.thi[r < NVY ? r : 0]); lo[r] = fl[r] ? P.tlo[r < NVY ? r : 0] : 0.0; hi[r] = fh[r] ? P.thi[r < NVY ? r : 0] : 0.0; }
+        else { fl[r] = false; fh[r] = true; lo[r] = 0.0; hi[r] = 0.0; }
         ncon += (fl[r] ? 1 : 0) + (fh[r] ? 1 : 0);
     }
     const double inv_ncon = 1.0 / dmax(ncon, 1.0);
@@ -836,7 +868,7 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
         MPC_UNROLL for (int i = 0; i < NR; i++) { double a = 0.0; MPC_UNROLL for (int j = 0; j < NR; j++) a += Hi[i][j] * gr[j]; y[i] = -a; }
     }
     MPC_UNROLL for (int r = 0; r < NC; r++) {
-        double v = w0[r]; MPC_UNROLL for (int c = 0; c < NR; c++) v += P.W[r][c] * y[c];
+        double v = w0[r]; MPC_UNROLL for (int c = 0; c < NR; c++) v += target_w<NVY, NGS>(P, r, c) * y[c];
         s_lo[r] = fl[r] ? dmax(v - lo[r], kSMin) : 1.0; s_hi[r] = fh[r] ? dmax(hi[r] - v, kSMin) : 1.0;
         l_lo[r] = fl[r] ? kMu0 * frcp(s_lo[r]) : 0.0; l_hi[r] = fh[r] ? kMu0 * frcp(s_hi[r]) : 0.0;
     }
@@ -848,7 +880,7 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
             const double smin = dmin(dmax(kWsKappa * delta, kWsSMinLo), kWsSMinHi), wmu = kWsMuFactor * smin * smin;
             MPC_UNROLL for (int c = 0; c < NR; c++) y[c] = tw[c * tws];
             MPC_UNROLL for (int r = 0; r < NC; r++) {
-                double v = w0[r]; MPC_UNROLL for (int c = 0; c < NR; c++) v += P.W[r][c] * y[c];
+                double v = w0[r]; MPC_UNROLL for (int c = 0; c < NR; c++) v += target_w<NVY, NGS>(P, r, c) * y[c];
                 s_lo[r] = fl[r] ? dmax(v - lo[r], smin) : 1.0; s_hi[r] = fh[r] ? dmax(hi[r] - v, smin) : 1.0;
                 l_lo[r] = fl[r] ? dmax(tw[(NR + r) * tws], wmu * frcp(s_lo[r])) : 0.0; l_hi[r] = fh[r] ? dmax(tw[(NR + NC + r) * tws], wmu * frcp(s_hi[r])) : 0.0;
             }
@@ -860,7 +892,7 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
         // reciprocals of the slacks once per iteration (v_rcp_f64 + Newton, mpc::frcp) instead of IEEE divisions
         double mu = 0.0, res_p = 0.0, res_s = 0.0, cres = 0.0, lmax = 0.0, grad[NR], sig[NC], r_lo[NC], r_hi[NC], is_lo[NC], is_hi[NC];
         MPC_UNROLL for (int r = 0; r < NC; r++) {
-            double v = w0[r]; MPC_UNROLL for (int c = 0; c < NR; c++) v += P.W[r][c] * y[c];
+            double v = w0[r]; MPC_UNROLL for (int c = 0; c < NR; c++) v += target_w<NVY, NGS>(P, r, c) * y[c];
             r_lo[r] = fl[r] ? v - s_lo[r] - lo[r] : 0.0; r_hi[r] = fh[r] ? v + s_hi[r] - hi[r] : 0.0;
             mu += s_lo[r] * l_lo[r] + s_hi[r] * l_hi[r];
             is_lo[r] = frcp(s_lo[r]); is_hi[r] = frcp(s_hi[r]);
@@ -872,7 +904,7 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
         mu *= inv_ncon;
         MPC_UNROLL for (int c = 0; c < NR; c++) {
             double a = gr[c]; MPC_UNROLL for (int j = 0; j < NR; j++) a += P.Hr[c][j] * y[j];
-            MPC_UNROLL for (int r = 0; r < NC; r++) a += (l_hi[r] - l_lo[r]) * P.W[r][c];
+            MPC_UNROLL for (int r = 0; r < NC; r++) a += (l_hi[r] - l_lo[r]) * target_w<NVY, NGS>(P, r, c);
             grad[c] = a; res_s = dmax(res_s, fabs(a));
         }
         iters = it;
@@ -882,7 +914,7 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
         if (lmax > kInfeasZ * gscale || !(fabs(mu) < 1.0e300)) { status = kInfeasible; break; }
         if (it == P.max_iter) { status = kMaxIter; break; }
         double Ht[NR][NR];
-        MPC_UNROLL for (int i = 0; i < NR; i++) { MPC_UNROLL for (int j = 0; j < NR; j++) { double a = P.Hr[i][j]; MPC_UNROLL for (int r = 0; r < NC; r++) a += sig[r] * P.W[r][i] * P.W[r][j]; Ht[i][j] = a; } }
+        MPC_UNROLL for (int i = 0; i < NR; i++) { MPC_UNROLL for (int j = 0; j < NR; j++) { double a = P.Hr[i][j]; MPC_UNROLL for (int r = 0; r < NC; r++) a += sig[r] * target_w<NVY, NGS>(P, r, i) * target_w<NVY, NGS>(P, r, j); Ht[i][j] = a; } }
         if (!sym_inverse<NR>(Ht)) { status = kInfeasible; break; }
         double dy[NR], ds_lo[NC], ds_hi[NC], dl_lo[NC], dl_hi[NC];
         double sm = 0.0, alpha = 1.0;
@@ -898,13 +930,13 @@ __device__ int target_lane(const PT &P, const double *usp, const double *ysp, co
             MPC_UNROLL for (int c = 0; c < NR; c++) rhs[c] = grad[c];
             MPC_UNROLL for (int r = 0; r < NC; r++) {
                 const double h = (-rc_hi[r] + l_hi[r] * r_hi[r]) * is_hi[r] + (rc_lo[r] + l_lo[r] * r_lo[r]) * is_lo[r];
-                MPC_UNROLL for (int c = 0; c < NR; c++) rhs[c] += h * P.W[r][c];
+                MPC_UNROLL for (int c = 0; c < NR; c++) rhs[c] += h * target_w<NVY, NGS>(P, r, c);
             }
             MPC_UNROLL for (int i = 0; i < NR; i++) { double a = 0.0; MPC_UNROLL for (int j = 0; j < NR; j++) a += Ht[i][j] * rhs[j]; dy[i] = -a; }
             // step to the boundary = 1 / m with m = max_i (-d_i / x_i); predictor capped at 1 (m >= 1), corrector at 1 / tau
             double m = pass == 0 ? 1.0 : kTau, s1 = 0.0;
             MPC_UNROLL for (int r = 0; r < NC; r++) {
-                double dv = 0.0; MPC_UNROLL for (int c = 0; c < NR; c++) dv += P.W[r][c] * dy[c];
+                double dv = 0.0; MPC_UNROLL for (int c = 0; c < NR; c++) dv += target_w<NVY, NGS>(P, r, c) * dy[c];
                 ds_hi[r] = fh[r] ? -r_hi[r] - dv : 0.0; ds_lo[r] = fl[r] ? r_lo[r] + dv : 0.0;
                 dl_hi[r] = fh[r] ? (-rc_hi[r] - l_hi[r] * ds_hi[r]) * is_hi[r] : 0.0;
                 dl_lo[r] = fl[r] ? (-rc_lo[r] - l_lo[r] * ds_lo[r]) * is_lo[r] : 0.0;

@@ -41,7 +41,7 @@
 
 namespace mpc {
 
-template <int NS, int NU, int NC, int NW, int IPW>
+template <int NS, int NU, int NC, int NW, int IPW, int XKEEP = 0>
 struct TpCfg {
     static constexpr int NI = NW * IPW;                              // instances per workgroup: NW waves, IPW instances each
     static constexpr int NV = NS + NU, NKF = NU * NS, NLI = NU * (NU + 1) / 2;
@@ -57,8 +57,9 @@ struct TpCfg {
     // state rows of an instance in HBM, [row][64 blocks]: s_lo s_hi l_lo l_hi dv (NC each) | u | z
     static constexpr int ST_SL = 0, ST_SH = NC, ST_LL = 2 * NC, ST_LH = 3 * NC, ST_DV = 4 * NC, ST_U = 5 * NC, ST_Z = 5 * NC + NU, ROWS_ST = 5 * NC + NV;
     // per-instance data the closed loop keeps in LDS across the steps of one launch (HBM copy at launch start / end):
-    // the warm start of the target problem (its size depends on ny, which this struct does not know: room for ny <= 8) + flag
-    static constexpr int KEEP_MAX = 2 * NU + 3 * (NS + NU + 8);
+    // the warm start of the target problem (its size depends on ny, which this struct does not know: room for ny <= 8) + flag;
+    // XKEEP: room for more of it - 3 per inequality user row of the target (loop_kernel_tp), 0 without such rows
+    static constexpr int KEEP_MAX = 2 * NU + 3 * (NS + NU + 8) + XKEEP;
     static constexpr size_t lds_bytes() { return sizeof(double) * (T_DOUBLES + NI * QN + NI * 4 + NI * KEEP_MAX) + sizeof(int) * (4 * NI + 4); }
 };
 
@@ -140,9 +141,9 @@ __device__ __forceinline__ double uni(double v)       // a wave-uniform value in
 }
 
 // Pointers into the dynamic LDS of the workgroup
-template <int NS, int NU, int NC, int NW, int IPW>
+template <int NS, int NU, int NC, int NW, int IPW, int XKEEP = 0>
 struct TpShared {
-    using Cfg = TpCfg<NS, NU, NC, NW, IPW>;
+    using Cfg = TpCfg<NS, NU, NC, NW, IPW, XKEEP>;
     static constexpr int NI = Cfg::NI;
     double *T, *q, *red, *keep; int *flag, *iflag, *iters, *keepflag, *misc;
     __device__ explicit TpShared(double *base)
@@ -165,8 +166,8 @@ enum : int { kTpOk0 = 1, kTpWarm = 2, kTpValid = 4 };
 // (written by wave 0, lanes < NI, before the call; a barrier is taken here).  On return wave 0, lane i < NI holds
 // status / iters of instance i; the final iterate is in the state rows (u0 = row ST_U.. at k = 0, z1 = ST_Z.. at k = 0).
 // wsg: state rows of this workgroup's instances [NI][ROWS_ST][64]; they hold the previous solve's iterate on entry.
-template <int NS, int NU, bool HASM, int NC, bool MASKED, int NW, int IPW>
-__device__ void tp_solve(const DevProblem &P, const TpShared<NS, NU, NC, NW, IPW> &sh, double *__restrict__ wsg,
+template <int NS, int NU, bool HASM, int NC, bool MASKED, int NW, int IPW, int XKEEP = 0>
+__device__ void tp_solve(const DevProblem &P, const TpShared<NS, NU, NC, NW, IPW, XKEEP> &sh, double *__restrict__ wsg,
                          int max_iter, int &status_o, int &iters_o)
 {
     using Cfg = TpCfg<NS, NU, NC, NW, IPW>;

@@ -812,22 +812,27 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
 // Same operations on the same numbers; sums over rows are taken in tree order.
 // ------------------------------------------------------------------------------------------------------------------------
 
-// per-row constants in LDS, filled once per launch (row r < NE: Aa[r][:] Qkf[r][:] Kfix[r][:] dmin dmax; row r < NCT: W[r][:] tlo thi)
-template <int NX, int NU, int NY, int ND>
+// per-row constants in LDS, filled once per launch (row r < NE: Aa[r][:] Qkf[r][:] Kfix[r][:] dmin dmax; row r < NCT: W[r][:] tlo thi).
+// NGS / NHS: the target's user rows (mpc_device.hpp:target_lane): NCT grows by NGS, the rows of W are NR = NU - NHS long
+template <int NX, int NU, int NY, int ND, int NGS = 0, int NHS = 0>
 struct Row16Tab {
-    static constexpr int NE = NX + ND, NR = NU, NCT = NX + NU + NY;
+    static constexpr int NE = NX + ND, NR = NU - NHS, NCT = NX + NU + NY + NGS;
     static constexpr int E_A = 0, E_Q = NE, E_K = 2 * NE, E_DMIN = 2 * NE + NY, E_DMAX = E_DMIN + 1, ESZ = E_DMAX + 1;
     static constexpr int T_W = 0, T_LO = NR, T_HI = NR + 1, TSZ = NR + 2;
     static constexpr int DOUBLES = NE * ESZ + NCT * TSZ;
+#ifdef MPC_ROW16_OFF      // diagnostic build only (tools/target_rows_cost.py): the wave-autonomous kernel on its lane = instance fallback
+    static constexpr bool fits = false;
+#else
     static constexpr bool fits = NE <= 16 && NCT <= 16;
+#endif
     // exchange space per instance (in the transposing buffer, which is idle outside the OCP solve)
     static constexpr int XCH = NE * NY + NE * NE;
 };
 
-template <int NX, int NU, int NY, int ND, class PT>
+template <int NX, int NU, int NY, int ND, int NGS = 0, int NHS = 0, class PT>
 __device__ __forceinline__ void row16_fill_tables(const PT &P, double *tab, int lane)
 {
-    using RT = Row16Tab<NX, NU, NY, ND>;
+    using RT = Row16Tab<NX, NU, NY, ND, NGS, NHS>;
     constexpr int NE = RT::NE;
     if (lane < NE) {
         double *e = tab + lane * RT::ESZ;
@@ -837,8 +842,14 @@ __device__ __forceinline__ void row16_fill_tables(const PT &P, double *tab, int 
     }
     if (lane < RT::NCT) {
         double *t = tab + NE * RT::ESZ + lane * RT::TSZ;
-        for (int c = 0; c < NU; c++) t[RT::T_W + c] = P.W[lane][c];
-        t[RT::T_LO] = P.tlo[lane]; t[RT::T_HI] = P.thi[lane];
+        constexpr int NVY = NX + NU + NY;
+        if (NGS == 0 || lane < NVY) {
+            for (int c = 0; c < RT::NR; c++) t[RT::T_W + c] = P.W[lane][c];
+            t[RT::T_LO] = P.tlo[lane]; t[RT::T_HI] = P.thi[lane];
+        } else if constexpr (NGS > 0) {      // the target's inequality rows: Gv_ss Zn y + w0 <= 0
+            for (int c = 0; c < RT::NR; c++) t[RT::T_W + c] = P.Wg[lane - NVY][c];
+            t[RT::T_LO] = -INFINITY; t[RT::T_HI] = 0.0;
+        }
     }
 }
 
@@ -902,12 +913,12 @@ __device__ __forceinline__ void kalman_row16(const PT &P, int r, bool slot_on, d
 // constraint row per lane.  dh / us_prev: this instance's data (the same in its 16 lanes); tw: its warm-start record in LDS
 // (y[NR] l_lo[NC] l_hi[NC] gr[NR] w0[NC]) with validity flag twv.  Returns the status (the same in the 16 lanes); v_out = row r of
 // [xs; us; ys] of the final point.
-template <int NX, int NU, int NY, int ND, class PT>
+template <int NX, int NU, int NY, int ND, int NGS = 0, int NHS = 0, class PT>
 __device__ __forceinline__ int target_row16(const PT &P, int r, const double *tab, const double *usp, const double *ysp, const double *dh,
                                             const double *us_prev, double *tw, int *twv, bool inst_on, double &v_out, int &iters)
 {
-    using RT = Row16Tab<NX, NU, NY, ND>;
-    constexpr int NV = NX + NU, NC = RT::NCT, NR = NU, NE = RT::NE;
+    using RT = Row16Tab<NX, NU, NY, ND, NGS, NHS>;
+    constexpr int NV = NX + NU, NC = RT::NCT, NR = RT::NR, NE = RT::NE;
     const bool row = r < NC;
     const int rr = row ? r : 0;
     const double *t = tab + NE * RT::ESZ + rr * RT::TSZ;
@@ -920,6 +931,11 @@ __device__ __forceinline__ int target_row16(const PT &P, int r, const double *ta
     MPC_UNROLL for (int i = 0; i < NX; i++) { double a = P.fxc[i]; MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Bd[i][j] * dh[j]; cx[i] = a; }
     MPC_UNROLL for (int i = 0; i < NY; i++) { double a = P.fyc[i]; MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Cd[i][j] * dh[j]; e[i] = a; }
     MPC_UNROLL for (int q = 0; q < NV; q++) { double a = 0.0; MPC_UNROLL for (int j = 0; j < NX; j++) a -= P.Ep[q][j] * cx[j]; vp[q] = a; }
+    if constexpr (NHS > 0) {      // the equality rows' right-hand side ch = h0_ss + Hd_ss dhat (mpc_device.hpp:target_lane)
+        double ch[NHS];
+        MPC_UNROLL for (int h = 0; h < NHS; h++) { double a = P.h0_ss[h]; MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Hd_ss[h][j] * dh[j]; ch[h] = a; }
+        MPC_UNROLL for (int q = 0; q < NV; q++) { double a = vp[q]; MPC_UNROLL for (int h = 0; h < NHS; h++) a -= P.Eh[q][h] * ch[h]; vp[q] = a; }
+    }
     MPC_UNROLL for (int i = 0; i < NY; i++) { double a = e[i]; MPC_UNROLL for (int j = 0; j < NX; j++) a += P.Cm[i][j] * vp[j]; yp[i] = a; }
     MPC_UNROLL for (int c = 0; c < NR; c++) {
         double a = 0.0;
@@ -934,6 +950,14 @@ __device__ __forceinline__ int target_row16(const PT &P, int r, const double *ta
     double w0 = 0.0;      // this lane's row of [vp; yp]
     MPC_UNROLL for (int q = 0; q < NV; q++) w0 = r == q ? vp[q] : w0;
     MPC_UNROLL for (int i = 0; i < NY; i++) w0 = r == NV + i ? yp[i] : w0;
+    if constexpr (NGS > 0) {      // the inequality rows at the particular solution: Gv_ss vp + Gd_ss dhat + g0_ss
+        MPC_UNROLL for (int g = 0; g < NGS; g++) {
+            double a = P.g0_ss[g];
+            MPC_UNROLL for (int j = 0; j < ND; j++) a += P.Gd_ss[g][j] * dh[j];
+            MPC_UNROLL for (int j = 0; j < NV; j++) a += P.Gv_ss[g][j] * vp[j];
+            w0 = r == NV + NY + g ? a : w0;
+        }
+    }
     const double ncon = row16_sum((fl ? 1.0 : 0.0) + (fh ? 1.0 : 0.0));
     const double inv_ncon = 1.0 / dmax(ncon, 1.0);
     {

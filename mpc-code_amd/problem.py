@@ -133,10 +133,29 @@ class LinearMPCProblem:
     Gu: Optional[np.ndarray] = None
     Gd: Optional[np.ndarray] = None
     g0: Optional[np.ndarray] = None
+    # affine user rows of the TARGET problem (User_g_ineq_SS / User_h_eq_SS, Target_Calc.py:87-110,139-155; MPC_code.py:295-300):
+    #   Gx_ss xs + Gu_ss us + Gd_ss dhat + g0_ss <= 0   (1 to 4 rows)     Hx_ss xs + Hu_ss us + Hd_ss dhat + h0_ss = 0   (fewer than nu rows)
+    # with ys = C xs + Cd dhat + fy_const already substituted; None: no rows
+    Gx_ss: Optional[np.ndarray] = None
+    Gu_ss: Optional[np.ndarray] = None
+    Gd_ss: Optional[np.ndarray] = None
+    g0_ss: Optional[np.ndarray] = None
+    Hx_ss: Optional[np.ndarray] = None
+    Hu_ss: Optional[np.ndarray] = None
+    Hd_ss: Optional[np.ndarray] = None
+    h0_ss: Optional[np.ndarray] = None
 
     @property
     def n_user_rows(self) -> int:
         return 0 if self.Gx is None else int(self.Gx.shape[0])
+
+    @property
+    def n_ss_ineq_rows(self) -> int:
+        return 0 if self.Gx_ss is None else int(self.Gx_ss.shape[0])
+
+    @property
+    def n_ss_eq_rows(self) -> int:
+        return 0 if self.Hx_ss is None else int(self.Hx_ss.shape[0])
 
     # ------------------------------------------------------------------ schedules
     def schedules(self, nsteps: int, k0: int = 0) -> Dict[str, np.ndarray]:
@@ -226,7 +245,7 @@ def problem_from_namespace(ns: Dict[str, Any], name: str = "") -> LinearMPCProbl
     """Classify an Ex-file namespace and emit the numeric descriptor (or raise)."""
     for bad in ("User_fxm_Cont", "User_fxm_Dis", "User_fym", "User_fxp_Dis", "User_fyp",
                 "User_fobj_Cont", "User_fobj_Dis", "User_fobj_Coll", "User_fssobj", "User_vfin",
-                "User_h_eq", "User_g_ineq_SS", "User_h_eq_SS", "r_x", "rss_y",
+                "User_h_eq", "r_x", "rss_y",
                 "def_pxmp", "def_pymp", "R_wn", "G_wn"):
         if _has(ns, bad) and ns[bad] is not None:
             raise UnsupportedProblem(f"'{bad}' is outside the batched linear hot path (later scope row)")
@@ -346,11 +365,32 @@ def problem_from_namespace(ns: Dict[str, Any], name: str = "") -> LinearMPCProbl
         else:
             K = _mat(ns["K"], nxd, ny, "K")
 
+    has_pxy = (_has(ns, "def_px") and ns["def_px"] is not None) or (_has(ns, "def_py") and ns["def_py"] is not None)
     Gx = Gu = Gd = g0 = None
     if _has(ns, "User_g_ineq") and ns["User_g_ineq"] is not None:
-        Gx, Gu, Gd, g0 = _affine_user_rows(ns["User_g_ineq"], nx, nu, ny, nd, C, Cd, fy_const)
-        if slacks or ns.get("TermCons", False) or (_has(ns, "def_px") and ns["def_px"] is not None) or (_has(ns, "def_py") and ns["def_py"] is not None):
+        Gx, Gu, Gd, g0 = _affine_user_rows(ns["User_g_ineq"], "User_g_ineq", nx, nu, ny, nd, C, Cd, fy_const)
+        if slacks or ns.get("TermCons", False) or has_pxy:
             raise UnsupportedProblem("User_g_ineq together with slacks, a terminal equality or horizon parameters is not carried")
+    # Rows of the target problem (Target_Calc.py:87-110,139-155).  They touch nothing but the target, so slacks, TermCons, Dumin / Dumax and
+    # OCP rows are carried with them.  With def_px / def_py the rows' constant would also need Jy py_0 (the target sees p_y_0): not carried.
+    ss_rows = {}
+    for fname, max_rows in (("User_g_ineq_SS", 4), ("User_h_eq_SS", None)):
+        if _has(ns, fname) and ns[fname] is not None:
+            if has_pxy:
+                raise UnsupportedProblem(f"{fname} together with def_px / def_py is not carried (the rows' constant would depend on p_y_0)")
+            ss_rows[fname] = _affine_user_rows(ns[fname], fname, nx, nu, ny, nd, C, Cd, fy_const, max_rows=max_rows)
+    Gx_ss = Gu_ss = Gd_ss = g0_ss = Hx_ss = Hu_ss = Hd_ss = h0_ss = None
+    if "User_g_ineq_SS" in ss_rows:
+        Gx_ss, Gu_ss, Gd_ss, g0_ss = ss_rows["User_g_ineq_SS"]
+    if "User_h_eq_SS" in ss_rows:
+        Hx_ss, Hu_ss, Hd_ss, h0_ss = ss_rows["User_h_eq_SS"]
+        nh = Hx_ss.shape[0]
+        if nh >= nu:
+            raise UnsupportedProblem(f"User_h_eq_SS: {nh} equality rows with nu = {nu}; the target keeps at least one free direction (nh < nu)")
+        # the steady-state rows and the equality rows together: [A-I, B; Hx, Hu] must have full row rank (the reduced space is its null space)
+        sv = np.linalg.svd(np.block([[A - np.eye(nx), B], [Hx_ss, Hu_ss]]), compute_uv=False)
+        if sv[-1] <= 1e-10 * max(1.0, sv[0]):
+            raise UnsupportedProblem("User_h_eq_SS: the equality rows are linearly dependent on each other or on the steady-state rows [A-I, B]")
     prob = LinearMPCProblem(
         nx=nx, nu=nu, ny=ny, nd=nd, nxp=nxp, N=N, h=h, Nsim=Nsim,
         A=A, B=B, C=C, Bd=Bd, Cd=Cd, fx_const=fx_const, fy_const=fy_const,
@@ -373,24 +413,26 @@ def problem_from_namespace(ns: Dict[str, Any], name: str = "") -> LinearMPCProbl
         plant_fx_cont=ns["User_fxp_Cont"] if nl_plant else None, plant_Mx=int(ns.get("Mx", 10)),
         TermCons=bool(ns.get("TermCons", False)), def_px=ns.get("def_px"), def_py=ns.get("def_py"),
         slacks=slacks, Ws=Ws, Gx=Gx, Gu=Gu, Gd=Gd, g0=g0,
+        Gx_ss=Gx_ss, Gu_ss=Gu_ss, Gd_ss=Gd_ss, g0_ss=g0_ss, Hx_ss=Hx_ss, Hu_ss=Hu_ss, Hd_ss=Hd_ss, h0_ss=h0_ss,
     )
     return prob
 
 
-def _affine_user_rows(fn, nx, nu, ny, nd, C, Cd, fy_const):
-    """User_g_ineq(x, u, y, d, t, px, py) <= 0 (Control_Calc.py:94-100; a row per stage k = 0..N-1 on (X[k], U[k], Y_k), :132-147) for the LINEAR hot path: the rows have
-    to be affine in (x, u, y, d) and independent of t, px, py (LinPar).  Traced once with symbols, then read off numerically - value at the origin, one unit vector per
-    argument - and checked at random points; y_k = C x_k + Cd d + fy_const is substituted.  Returns (Gx, Gu, Gd, g0)."""
+def _affine_user_rows(fn, fname, nx, nu, ny, nd, C, Cd, fy_const, max_rows=4):
+    """Affine user rows for the LINEAR hot path: User_g_ineq(x, u, y, d, t, px, py) <= 0 (Control_Calc.py:94-100; a row per stage k = 0..N-1 on (X[k], U[k], Y_k), :132-147),
+    and the target's User_g_ineq_SS <= 0 / User_h_eq_SS = 0 on (Xs, Us, Ys) (Target_Calc.py:87-110).  The rows have to be affine in (x, u, y, d) and independent of t, px, py
+    (LinPar).  Traced once with symbols, then read off numerically - value at the origin, one unit vector per argument - and checked at random points; y = C x + Cd d +
+    fy_const is substituted.  ``fname`` names the function in the messages; ``max_rows`` None: no upper limit here.  Returns (Gx, Gu, Gd, g0)."""
     from . import symtrace as st
     vx, vu, vy, vd, vt = st.symvec("x", nx), st.symvec("u", nu), st.symvec("y", ny), st.symvec("d", nd), st.Sym.var("t")
     col, zero = st.SymMat.col, (lambda n: st.SymMat.zeros(n))
     try:
         rows = st.flatten(fn(col(vx), col(vu), col(vy), col(vd), vt, zero(nx), zero(ny)))
     except Exception as e:      # noqa: BLE001
-        raise UnsupportedProblem(f"User_g_ineq cannot be traced: {e}") from e
+        raise UnsupportedProblem(f"{fname} cannot be traced: {e}") from e
     ng = len(rows)
-    if ng < 1 or ng > 4:
-        raise UnsupportedProblem("User_g_ineq: between one and four rows are carried")
+    if ng < 1 or (max_rows is not None and ng > max_rows):
+        raise UnsupportedProblem(f"{fname}: between one and {max_rows} rows are carried (it has {ng})" if max_rows is not None else f"{fname}: it has no rows")
     nz = nx + nu + ny + nd
     names = [f"x[{i}]" for i in range(nx)] + [f"u[{i}]" for i in range(nu)] + [f"y[{i}]" for i in range(ny)] + [f"d[{i}]" for i in range(nd)]
 
@@ -403,6 +445,6 @@ def _affine_user_rows(fn, nx, nu, ny, nd, C, Cd, fy_const):
     for _ in range(4):
         z = rng.normal(size=nz) * 3.0
         if np.abs(ev(z, t=rng.normal()) - (c0 + J @ z)).max() > 1e-9 * (1.0 + np.abs(J).max() * 10.0):
-            raise UnsupportedProblem("User_g_ineq: only rows that are affine in (x, u, y, d) and independent of t are carried on the linear path")
+            raise UnsupportedProblem(f"{fname}: only rows that are affine in (x, u, y, d) and independent of t are carried on the linear path")
     Jx, Ju, Jy, Jd = J[:, :nx], J[:, nx:nx + nu], J[:, nx + nu:nx + nu + ny], J[:, nx + nu + ny:]
     return Jx + Jy @ C, Ju, (Jd + Jy @ Cd if nd else np.zeros((ng, 0))), c0 + Jy @ fy_const
