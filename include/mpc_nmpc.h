@@ -69,7 +69,7 @@ int nmpc_run(nmpc_handle *h, int32_t k0, int32_t nsteps, int32_t max_sqp, double
 int nmpc_sync(nmpc_handle *h);
 /* which closed-loop kernel nmpc_run launches: 1 = one instance per lane (any model), 3 = wave-autonomous (one wave owns four instances
  * for a launch, lane = stage, QP on the matrix cores), 4 = split pipeline (per step one lane-style launch for estimator / target /
- * plant and one wave-style launch for linearisation + QP); 3 and 4 need model state <= 4, nu <= 2, N <= 64 and no input-move form.
+ * plant and one wave-style launch for linearisation + QP); 3 and 4 need a stage state (model state + user inequality rows, User_g_ineq) <= 4, nu <= 2, N <= 64 and no input-move form.
  * 0 = auto when the model fits: 3 while one round of its waves holds the batch (16 instances per CU: 4096 on an MI355X), 4 beyond;
  * else 1.  nmpc_get_kernel returns the one in force */
 int nmpc_set_kernel(nmpc_handle *h, int32_t kernel);

@@ -10,7 +10,8 @@ Covered: continuous-time model and plant (``User_fxm_Cont``, ``User_fym``, ``Use
 entering the model non-linearly (``offree = "nl"``: the estimate ``dhat`` is an argument of the model, ``Utilities.py:126-129``),
 quadratic stage cost on ``x - xs`` and ``u - us`` (``Q``, ``R``; no terminal cost: ``defVfin`` returns 0 without ``A``,
 ``Utilities.py:398-399``), quadratic target cost (``Qss``, ``Rss``), bounds on u, x, y (outputs that are single states),
-saturation of ``dhat``, extended Kalman filter (``Estimator.py:313-386``).  Anything else raises ``UnsupportedProblem``.
+saturation of ``dhat``, extended Kalman filter (``Estimator.py:313-386``), user inequality rows ``User_g_ineq(x, u, y, d, t, px, py) <= 0`` at every
+stage of the horizon (``Control_Calc.py:94-100,132-147``; carried as stage states).  Anything else raises ``UnsupportedProblem``.
 """
 from __future__ import annotations
 
@@ -86,6 +87,7 @@ class NonlinearMPCProblem:
     def_pxp: Optional[Callable] = None
     def_pyp: Optional[Callable] = None
     funcs: Dict[str, Any] = field(default_factory=dict)      # the Ex-file's own Python functions (host-side checks)
+    g_ineq: List[st.Sym] = field(default_factory=list)       # user inequality rows G(x, u, Fy_model(x, u, d, t), d, t, 0, 0) <= 0, stages 0..N-1
 
     def __repr__(self):      # the traced expressions print as whole trees: keep them out of reprs (pytest renders them on a failure)
         return f"NonlinearMPCProblem({self.name!r}, nx={self.nx}, nu={self.nu}, ny={self.ny}, nd={self.nd}, N={self.N}, discrete={self.discrete})"
@@ -98,6 +100,11 @@ class NonlinearMPCProblem:
         if self.f is not None:
             self.f_x = st.jacobian(self.f, self.vx); self.f_u = st.jacobian(self.f, self.vu); self.f_d = st.jacobian(self.f, self.vd)
             self.h_x = st.jacobian(self.hy, self.vx); self.h_d = st.jacobian(self.hy, self.vd)
+        self.g_x = st.jacobian(self.g_ineq, self.vx); self.g_u = st.jacobian(self.g_ineq, self.vu)
+
+    @property
+    def ng(self) -> int:
+        return len(self.g_ineq)
 
     @property
     def nw(self) -> int:
@@ -161,7 +168,7 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
     """Classify a non-linear Ex-file namespace (reference MPC_code.py:84-257 probes) and trace its functions."""
     has = lambda k: k in ns and ns[k] is not None and not k.startswith("__")
     for bad in ("User_fobj_Cont", "User_fobj_Dis", "User_fobj_Coll", "User_fssobj",
-                "User_g_ineq", "User_h_eq", "User_g_ineq_SS", "User_h_eq_SS", "r_x", "rss_y", "def_px", "def_py", "def_pxmp", "def_pymp", "A", "G_wn"):
+                "User_h_eq", "User_g_ineq_SS", "User_h_eq_SS", "r_x", "rss_y", "def_px", "def_py", "def_pxmp", "def_pymp", "A", "G_wn"):
         if has(bad):
             raise UnsupportedProblem(f"'{bad}' is outside the non-linear path built so far")
     if has("R_wn"):
@@ -238,6 +245,18 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
             at0 = float(np.asarray(st.evaluate([hy_user[i]], {**{f"x[{j}]": 0.0 for j in range(nx)}, **{f"u[{j}]": 0.0 for j in range(nu)}, **{f"d[{j}]": 0.0 for j in range(nd)}, "t": 0.0})[0]))
             if any(not e.is_const(0.0) for e in others) or at0 != 0.0:
                 raise UnsupportedProblem(f"bounded output {i} is state {c} plus something else (d, a constant): its bounds are not a box on the state")
+    du_bounded = has("Dumin") or has("Dumax")
+    # user inequality rows of the OCP, G(x_k, u_k, y_k, d, t, px_k, py_k) <= 0 for k = 0..N-1 (Control_Calc.py:94-100,132-147; MPC_code.py:306-314), with
+    # y = Fy_model(x, u, d, t) substituted (with offree = 'lin' the + Cd d is part of it) and px = py = 0 (def_px / def_py are refused on this path).
+    # Each row is one more stage state w_{k+1} = G(x_k, u_k) with the box w <= 0, linearised along the trajectory in every SQP iteration
+    # (csrc/mpc_nmpc.hip).
+    g_ineq = []
+    if has("User_g_ineq"):
+        g_ineq = _trace(ns["User_g_ineq"], (col(vx), col(vu), col(hy), col(vd), vt, zero(nx), zero(ny)))
+        if not g_ineq or len(g_ineq) > 4:
+            raise UnsupportedProblem("User_g_ineq: between one and four rows are carried")
+        if nx + (nu if (has("S") and not has("R")) or du_bounded else 0) + len(g_ineq) > 8:
+            raise UnsupportedProblem("User_g_ineq: the stage state (nx, + nu in the input-move form, + rows) exceeds 8")
     if has("R"):
         R, DUForm = _mat(ns["R"], nu, nu, "R"), False
     elif has("S"):
@@ -250,7 +269,6 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
         Rss, DUssForm = _mat(ns["Sss"], nu, nu, "Sss"), True  # MPC_code.py:216-218
     else:
         Rss, DUssForm = np.zeros((nu, nu)), False
-    du_bounded = has("Dumin") or has("Dumax")
     Pf = np.zeros((nx, nx))
     if has("User_vfin"):      # Vfin(dx, xs) with dx = X[N] - xs (Control_Calc.py:193-210): accepted when it is a quadratic form of dx alone
         vdx = st.symvec("dx", nx)
@@ -277,7 +295,7 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
         x0_p=_vec(ns["x0_p"], nxp, 0.0), x0_m=_vec(ns["x0_m"], nx, 0.0), u0=_vec(ns["u0"], nu, 0.0),
         dhat0=_vec(ns.get("dhat0"), nd, 0.0) if has("dhat0") else np.zeros(nd),
         max_iter=int(ns.get("Sol_itmax", 100)), defSP=ns.get("defSP"), R_wn=(_mat(ns["R_wn"], ny, ny, "R_wn") if has("R_wn") else None), name=name or str(ns.get("__name__", "")), ycols=ycols,
-        funcs={k: ns[k] for k in ("User_fxm_Cont", "User_fxm_Dis", "User_fym", "User_fxp_Cont", "User_fxp_Dis", "User_fyp") if has(k)},
+        funcs={k: ns[k] for k in ("User_fxm_Cont", "User_fxm_Dis", "User_fym", "User_fxp_Cont", "User_fxp_Dis", "User_fyp", "User_g_ineq") if has(k)}, g_ineq=g_ineq,
         discrete=discrete, plant_discrete=plant_discrete, offree=offree, Bd=Bd, Cd=Cd, estimator=est,
         K=_mat(ns["K"], nx + nd, ny, "K") if est == "lue" else None, DUForm=DUForm, DUssForm=DUssForm,
         Dumin=_vec(ns.get("Dumin"), nu, -INF) if du_bounded else None, Dumax=_vec(ns.get("Dumax"), nu, INF) if du_bounded else None, Pf=Pf,
