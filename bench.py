@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: closed-loop MPC steps/s over a batch, LMPC-CSTR, N=50 (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A *step* is one closed-loop step (estimator + target + OCP + plant, reference MPC_code.py:485-827)
 of every instance of the per-GPU batch.  Workload at N=1: BASELINE.json configs[1] - the shipped
@@ -26,8 +26,14 @@ seeded, so two builds run with the same arguments can be compared output for out
 Prints ONE JSON line (rank 0).  `roofline` prices the fused closed-loop kernel against HBM with the
 algorithmic bytes of SURVEY.md section 8d (4 968 B per instance-step); `traffic` is the measured HBM-side
 traffic per launch, scaled from the per-instance-step figure of the committed PMC summary of this kernel.
-`cpu_baseline` times oracle/mpc_oracle.c (a C port of the same algorithm, -O3 -march=native -fopenmp
-- the reference's own CasADi/IPOPT path cannot run here) on all host cores and on one.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds what takes runs of its own: `cpu_baseline` times oracle/mpc_oracle.c (a C port of the same
+algorithm, -O3 -march=native -fopenmp - the reference's own CasADi/IPOPT path cannot run here) on all host
+cores and on one (every config; --no-cpu-baseline leaves it out); at the default lmpc workload on one GPU,
+`other_configs` carries BASELINE configs[2..4], each measured by a child `--config ... --full` run
+(--no-other-configs leaves them out); the split pipelines of --config nmpc / enmpc / mhe get their
+per-launch timing passes, which their `roofline` is priced from (without --full it is null there).
 """
 from __future__ import annotations
 
@@ -294,7 +300,7 @@ def other_configs(args):
     out = {}
     for name in ("nmpc", "enmpc", "mhe"):
         cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--min-seconds", str(args.min_seconds), "--cpu-seconds", str(min(args.cpu_seconds, 2.5))] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
+               "--min-seconds", str(args.min_seconds), "--cpu-seconds", str(min(args.cpu_seconds, 2.5)), "--full"] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
         t0 = time.perf_counter()
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -401,7 +407,7 @@ def main_enmpc(args):
     if comm is not None:
         allU = s.allgather_log("U", 0, K)
         assert np.array_equal(allU[rank], s.get_log("U")[:K]), "all-gather of U corrupted the data"
-    if kern == 2:
+    if kern == 2 and args.full:
         # the split pipeline's launches one by one: passes of the same K steps with HIP events around every launch (which puts the batch on one
         # stream - the timed regions above run it in groups on streams of their own, where launches overlap and have no duration of their own)
         s.time_kernels(True)
@@ -413,22 +419,34 @@ def main_enmpc(args):
         st = {k: s.get_log(k)[:K] for k in ("STATUS_DYN", "STATUS_SS", "STATUS_MHE", "ITERS_DYN", "ITERS_SS", "ITERS_MHE")}
         nw_mean = float(np.mean([min(k + 1, p.N_mhe) for k in range(K)]))
         parts = enmpc_alg(p, float(st["ITERS_DYN"].mean()), float(st["ITERS_SS"].mean()), float(st["ITERS_MHE"].mean()), nw_mean)
-        if kern == 2:      # the dominant kernel of the split pipeline: one launch = one phase of one step of every instance
-            share = np.mean(pms, axis=0)
-            j = int(np.argmax(share))
-            kname = ("enmpc_mhe_kernel", "enmpc_target_kernel", "enmpc_ocp_kernel")[j]
-            kdesc = ("%s (split pipeline: per step one launch for the estimator, one for the target - lane = instance - and one for OCP + plant; estimator and OCP with one "
-                     "wave per instance, lane = stage, Riccati recursion over the lanes; device time by phase: estimator %.0f %%, target %.0f %%, OCP + plant %.0f %%)"
-                     % (kname, *(100.0 * share / share.sum())))
-            ab, fl = parts[j]
-            per_launch_s, units, launches = float(share[j]) / K * 1e-3, B, K * len(pms)
-        else:
-            kname, kdesc = "enmpc_loop_kernel", "enmpc_loop_kernel (one wave = one instance, lane = stage; every phase of all K steps in one launch)"
-            ab, fl = parts[3]
-            per_launch_s, units, launches = float(np.mean(kms)) * 1e-3, B * K, len(times)
-        achieved = ab * units / per_launch_s / 1e9
-        tflops = fl * units / per_launch_s / 1e12
-        traffic, traffic_src = measured_traffic(kname, units, os.path.join(ROOT, "profiles", "%s_%s_pmc_summary.json" % (PROFILE_ROUND, args.config)))
+        roofline = None
+        if kern != 2 or pms:      # the split pipeline is priced from its per-launch passes above (--full)
+            if kern == 2:      # the dominant kernel of the split pipeline: one launch = one phase of one step of every instance
+                share = np.mean(pms, axis=0)
+                j = int(np.argmax(share))
+                kname = ("enmpc_mhe_kernel", "enmpc_target_kernel", "enmpc_ocp_kernel")[j]
+                kdesc = ("%s (split pipeline: per step one launch for the estimator, one for the target - lane = instance - and one for OCP + plant; estimator and OCP with one "
+                         "wave per instance, lane = stage, Riccati recursion over the lanes; device time by phase: estimator %.0f %%, target %.0f %%, OCP + plant %.0f %%)"
+                         % (kname, *(100.0 * share / share.sum())))
+                ab, fl = parts[j]
+                per_launch_s, units, launches = float(share[j]) / K * 1e-3, B, K * len(pms)
+            else:
+                kname, kdesc = "enmpc_loop_kernel", "enmpc_loop_kernel (one wave = one instance, lane = stage; every phase of all K steps in one launch)"
+                ab, fl = parts[3]
+                per_launch_s, units, launches = float(np.mean(kms)) * 1e-3, B * K, len(times)
+            achieved = ab * units / per_launch_s / 1e9
+            tflops = fl * units / per_launch_s / 1e12
+            traffic, traffic_src = measured_traffic(kname, units, os.path.join(ROOT, "profiles", "%s_%s_pmc_summary.json" % (PROFILE_ROUND, args.config)))
+            roofline = {"bound": "issue", "priced_against": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": getattr(measured_traffic, "stale", None),
+                        "kernel": kdesc, "launches": launches, "avg_launch_ms": per_launch_s * 1e3,
+                        "issue": issue_roofline(os.path.join(ROOT, "profiles", "%s_%s_pmc_summary.json" % (PROFILE_ROUND, args.config)), per_launch_s, units / float(cfg["batch"]), alg_flops_per_launch=fl * units),
+                        "launch_timing": ("HIP events around every launch of %d separate passes of the same %d steps on one stream (the timed regions run the batch in "
+                                          "groups on streams of their own)" % (len(pms), K)) if kern == 2 else "HIP events around the timed regions' launches",
+                        "alg_bytes_per_step": ab, "instance_steps_per_launch": units, "device_ms_per_run": float(np.mean(kms)),
+                        "fp64": {"achieved_tflops": tflops, "peak_tflops": FP64_PEAK_TFLOPS, "frac": tflops / FP64_PEAK_TFLOPS, "alg_flops_per_step": fl},
+                        "note": "the path is bound by fp64 vector issue and dependent-instruction latency (Runge-Kutta sensitivities, Riccati recursion over the lanes), "
+                                "not by HBM: 'achieved' prices the state the priced kernel carries in and out per instance-step (DESIGN.md section 10), 'fp64' the "
+                                "algorithmic flops of the run's iteration counts against the vector fp64 peak"}
         out = {"metric": cfg["metric"], "value": B * world * K / dt, "unit": "steps/s", "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": dt / K * 1e3,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                "config": {"workload": "Ex_ENMPC (isothermal reactor, nx=2,nu=1,ny=2,nd=2; continuous-time economic cost integrated over every shooting interval, "
@@ -438,19 +456,10 @@ def main_enmpc(args):
                           "parallelism": "instances sharded over %d GPU(s), one process each; RCCL all-gather of U inside the timed region" % world,
                           "rccl_ranks": (s.comm_rank()[1] if comm is not None else 1),
                           "timed_region_ms": {"median": dt * 1e3, "min": float(np.min(times)) * 1e3, "max": float(np.max(times)) * 1e3}},
-               "roofline": {"bound": "issue", "priced_against": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": getattr(measured_traffic, "stale", None),
-                            "kernel": kdesc, "launches": launches, "avg_launch_ms": per_launch_s * 1e3,
-                            "issue": issue_roofline(os.path.join(ROOT, "profiles", "%s_%s_pmc_summary.json" % (PROFILE_ROUND, args.config)), per_launch_s, units / float(cfg["batch"]), alg_flops_per_launch=fl * units),
-                            "launch_timing": ("HIP events around every launch of %d separate passes of the same %d steps on one stream (the timed regions run the batch in "
-                                              "groups on streams of their own)" % (len(pms), K)) if kern == 2 else "HIP events around the timed regions' launches",
-                            "alg_bytes_per_step": ab, "instance_steps_per_launch": units, "device_ms_per_run": float(np.mean(kms)),
-                            "fp64": {"achieved_tflops": tflops, "peak_tflops": FP64_PEAK_TFLOPS, "frac": tflops / FP64_PEAK_TFLOPS, "alg_flops_per_step": fl},
-                            "note": "the path is bound by fp64 vector issue and dependent-instruction latency (Runge-Kutta sensitivities, Riccati recursion over the lanes), "
-                                    "not by HBM: 'achieved' prices the state the priced kernel carries in and out per instance-step (DESIGN.md section 10), 'fp64' the "
-                                    "algorithmic flops of the run's iteration counts against the vector fp64 peak"},
+               "roofline": roofline,
                "solver": {"frac_solved_dyn": float((st["STATUS_DYN"] == 0).mean()), "frac_solved_ss": float((st["STATUS_SS"] == 0).mean()), "frac_solved_mhe": float((st["STATUS_MHE"] == 0).mean()),
                           "mean_iters_dyn": float(st["ITERS_DYN"].mean()), "mean_iters_ss": float(st["ITERS_SS"].mean()), "mean_iters_mhe": float(st["ITERS_MHE"].mean())}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import enmpc_oracle as eo
             import enmpc_oracle_c as eoc
@@ -516,7 +525,7 @@ def main_nmpc(args):
             break
     dt = float(np.median(times))
     kms1 = kms
-    if split:
+    if split and args.full:
         # the wave-style launches one by one: separate passes of the same K steps, every wave-style launch bracketed by its own HIP events (which puts the
         # batch on one stream - the timed regions above run it in groups on streams of their own, where launches overlap and have no duration of their own)
         s.time_kernels(True); kms1 = []
@@ -529,28 +538,36 @@ def main_nmpc(args):
     state = p.nxp + p.nx + p.nd + ne * ne + p.nu + p.nx + p.nu
     ab = (2 * state + 2 * p.nw + p.ny + p.nu) * 8              # state in + out, shifted trajectory in + out, set points
     summary = os.path.join(ROOT, "profiles", PROFILE_ROUND + "_nmpc_pmc_summary.json")
-    if split:
-        # the dominant kernel of the split pipeline: one launch = linearisation + QP of one step of every instance
-        per_launch_s = float(np.mean(wms)) * 1e-3
-        units = B
-        kname = "nmpc_loop_kernel_wv<true>"
-        kdesc = ("nmpc_loop_kernel_wv<true> (split pipeline, the wave-style launch of a step: one wave owns four instances, lane = stage - two "
-                 "instances side by side for N <= 32 -, RK4 sensitivities into LDS, QP on the matrix cores; %.0f %% of the device time of a "
-                 "run, the lane-style launch nmpc_step_lane_kernel - estimator, target, plant - is the rest)" % (100.0 * np.mean(wms) * wn / np.mean(kms1)))
-        note = ("algorithmic bytes: resident state in and out + the shifted trajectory in and out + set points, per instance-step; one launch of "
-                "this kernel advances every instance by one step.  The kernel is bound by dependent fp64 chains (RK4 sensitivities, Riccati "
-                "recursions on one wave per SIMD), not by HBM: its measured traffic is the trajectories / multipliers (warm start rows) it loads "
-                "and stores per launch and the exchange buffers")
-    else:
-        per_launch_s = float(np.mean(kms)) * 1e-3
-        units = B * K
-        kname = "nmpc_loop_kernel"
-        kdesc = "nmpc_loop_kernel (one instance per lane, all steps in one launch; helper waves share the stage linearisations up to one workgroup per CU)"
-        note = ("algorithmic bytes: resident state in and out + the shifted trajectory in and out + set points.  Measured traffic is two "
-                "orders above them: this kernel is the instance-per-lane design, its Riccati workspace (20 KB per instance) and the "
-                "linearisation slab (7 KB) stream through HBM in every sweep")
-    achieved = ab * units / per_launch_s / 1e9
-    traffic, traffic_src = measured_traffic(kname, units, summary)
+    roofline = None
+    if not split or wms:      # the split pipeline is priced from its per-launch passes above (--full)
+        if split:
+            # the dominant kernel of the split pipeline: one launch = linearisation + QP of one step of every instance
+            per_launch_s = float(np.mean(wms)) * 1e-3
+            units = B
+            kname = "nmpc_loop_kernel_wv<true>"
+            kdesc = ("nmpc_loop_kernel_wv<true> (split pipeline, the wave-style launch of a step: one wave owns four instances, lane = stage - two "
+                     "instances side by side for N <= 32 -, RK4 sensitivities into LDS, QP on the matrix cores; %.0f %% of the device time of a "
+                     "run, the lane-style launch nmpc_step_lane_kernel - estimator, target, plant - is the rest)" % (100.0 * np.mean(wms) * wn / np.mean(kms1)))
+            note = ("algorithmic bytes: resident state in and out + the shifted trajectory in and out + set points, per instance-step; one launch of "
+                    "this kernel advances every instance by one step.  The kernel is bound by dependent fp64 chains (RK4 sensitivities, Riccati "
+                    "recursions on one wave per SIMD), not by HBM: its measured traffic is the trajectories / multipliers (warm start rows) it loads "
+                    "and stores per launch and the exchange buffers")
+        else:
+            per_launch_s = float(np.mean(kms)) * 1e-3
+            units = B * K
+            kname = "nmpc_loop_kernel"
+            kdesc = "nmpc_loop_kernel (one instance per lane, all steps in one launch; helper waves share the stage linearisations up to one workgroup per CU)"
+            note = ("algorithmic bytes: resident state in and out + the shifted trajectory in and out + set points.  Measured traffic is two "
+                    "orders above them: this kernel is the instance-per-lane design, its Riccati workspace (20 KB per instance) and the "
+                    "linearisation slab (7 KB) stream through HBM in every sweep")
+        achieved = ab * units / per_launch_s / 1e9
+        traffic, traffic_src = measured_traffic(kname, units, summary)
+        roofline = {"bound": "issue", "priced_against": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": getattr(measured_traffic, "stale", None),
+                    "kernel": kdesc, "launches": (wn * len(wms)) if split else len(times), "avg_launch_ms": per_launch_s * 1e3, "alg_bytes_per_step": ab,
+                    "issue": issue_roofline(summary, per_launch_s, units / 16384.0) if split else None,
+                    "launch_timing": ("HIP events around every wave-style launch of %d separate passes of the same %d steps on one stream (the timed regions run the batch in "
+                                      "groups on streams of their own)" % (len(wms), K)) if split else "HIP events around the timed regions' launches",
+                    "instance_steps_per_launch": units, "note": note}
     out = {"metric": "closed-loop NMPC steps/sec over batch, Ex_NMPC N=30 (BASELINE configs[3])", "value": B * K / dt, "unit": "steps/s", "n_gpus": 1,
            "steps": K, "warmup": W, "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
            "data": "synthetic",
@@ -559,15 +576,10 @@ def main_nmpc(args):
                       "batch_per_gpu": B, "horizon": p.N, "steps_per_run": K, "kernel": kern, "stream_groups": args.groups, "max_sqp": args.max_sqp, "repeats": len(times),
                       "timed_region_ms": {"median": dt * 1e3, "min": float(np.min(times)) * 1e3, "max": float(np.max(times)) * 1e3},
                       "device_ms_per_run": float(np.mean(kms))},
-           "roofline": {"bound": "issue", "priced_against": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src, "traffic_stale": getattr(measured_traffic, "stale", None),
-                        "kernel": kdesc, "launches": (wn * len(wms)) if split else len(times), "avg_launch_ms": per_launch_s * 1e3, "alg_bytes_per_step": ab,
-                        "issue": issue_roofline(summary, per_launch_s, units / 16384.0) if split else None,
-                        "launch_timing": ("HIP events around every wave-style launch of %d separate passes of the same %d steps on one stream (the timed regions run the batch in "
-                                          "groups on streams of their own)" % (len(wms), K)) if split else "HIP events around the timed regions' launches",
-                        "instance_steps_per_launch": units, "note": note},
+           "roofline": roofline,
            "solver": {"frac_solved": float((st == 0).mean()), "frac_maxiter": float((st == 1).mean()), "frac_infeasible_hold": float((st == 2).mean()),
                       "mean_sqp": float(sqp.mean()), "mean_ipm_iters_last_qp": float(it.mean())}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import warnings
         import nmpc_oracle as no
@@ -606,7 +618,9 @@ def main():
     ap.add_argument("--loop-kernel", type=int, default=0, help="0: library default, 1: instance per lane, 2: horizon-parallel, 3: wave-autonomous")
     ap.add_argument("--repeats", type=int, default=1, help="timed regions of --steps steps each, the median reported (0: as many as fill --min-seconds)")
     ap.add_argument("--min-seconds", type=float, default=3.0, help="with --repeats 0: GPU time to spend in timed regions (of this workload and of each of the other configs' child runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the CPU baselines, the other BASELINE configs next to the "
+                    "metric workload, the per-launch timing passes of the split pipelines (a plain run: set-up, warm-up, the timed steps, --dump-outputs, the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--force-dist", action="store_true", help="create the RCCL communicator even for one rank: exercises the N>1 code path on a 1-GPU box")
     ap.add_argument("--config", default="lmpc", choices=["lmpc", "nmpc", "enmpc", "mhe"], help="lmpc: the metric workload (BASELINE configs[1]); nmpc: "
                     "configs[2], Ex_NMPC N=30, batch 16384, one real-time SQP iteration per step, one GPU; enmpc: configs[3], Ex_ENMPC N=40, batch "
@@ -615,7 +629,7 @@ def main():
     ap.add_argument("--groups", type=int, default=0, help="nmpc / enmpc / mhe: groups of the batch on HIP streams of their own (0: the library's choice; 1: one stream, "
                     "as the profiles need it - overlapping launches have no duration of their own)")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="nmpc / enmpc / mhe: host seconds per thread count of the CPU baseline's bounded sample")
-    ap.add_argument("--no-other-configs", action="store_true", help="lmpc on one GPU: do not measure BASELINE configs[2..4] next to the metric workload")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, lmpc on one GPU: do not measure BASELINE configs[2..4] next to the metric workload")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: every rank goes through the rendezvous only and rank 0 prints who was there (launcher test)")
     args = ap.parse_args()
@@ -638,7 +652,7 @@ def main():
         B = args.total_batch // world
     use_dist = world > 1 or args.force_dist
     others = None
-    if world == 1 and not args.force_dist and not args.no_other_configs and B == B_PER_GPU and not strong:
+    if args.full and world == 1 and not args.force_dist and not args.no_other_configs and B == B_PER_GPU and not strong:
         others = other_configs(args)      # child processes, before this one touches the GPU
 
     import mpc_code_amd as m
@@ -731,7 +745,7 @@ def main():
                        "frac_solved": float((st == 0).mean()), "frac_maxiter": float((st == 1).mean()),
                        "frac_infeasible_hold": float((st == 2).mean())},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prob, x0, K)
         if others is not None:
             out["other_configs"] = others

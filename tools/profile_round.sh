@@ -21,7 +21,7 @@ if [ "${2:-}" = "nmpc" ]; then
     python3 tools/pmc_summary.py nmpc_loop_kernel_wv "$OUT/${TAG}_nmpc_pmc_summary.json" 16384 "$CMD" "$OUT"/pmc_* > /dev/null 2>&1; head -c 1500 "$OUT/${TAG}_nmpc_pmc_summary.json"
     # the bench line last: it cites the PMC summary of the same round (bench.py: PROFILE_ROUND), which has to exist first
     cp "$OUT/${TAG}_nmpc_pmc_summary.json" profiles/
-    timeout 600 python3 bench.py --config nmpc --steps 20 --warmup 2 > "$OUT/${TAG}_nmpc_bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -c 600 "$OUT/${TAG}_nmpc_bench.json"
+    timeout 600 python3 bench.py --config nmpc --steps 20 --warmup 2 --full > "$OUT/${TAG}_nmpc_bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -c 600 "$OUT/${TAG}_nmpc_bench.json"
     head -5 "$OUT/${TAG}_nmpc_kernel_stats.csv"
     exit 0
 fi
@@ -39,7 +39,7 @@ if [ "${2:-}" = "enmpc" ] || [ "${2:-}" = "mhe" ]; then      # the economic work
     KERN=enmpc_ocp_kernel; [ "$CFG" = "mhe" ] && KERN=enmpc_mhe_kernel      # the kernel bench.py prices: the largest share of the device time
     python3 tools/pmc_summary.py $KERN "$OUT/${TAG}_${CFG}_pmc_summary.json" $B "$CMD" "$OUT"/pmc_* > /dev/null 2>&1; head -c 1200 "$OUT/${TAG}_${CFG}_pmc_summary.json"
     cp "$OUT/${TAG}_${CFG}_pmc_summary.json" profiles/      # (the bench line last: it cites this summary)
-    timeout 600 python3 bench.py --config $CFG --steps 20 --warmup 2 > "$OUT/${TAG}_${CFG}_bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -c 600 "$OUT/${TAG}_${CFG}_bench.json"
+    timeout 600 python3 bench.py --config $CFG --steps 20 --warmup 2 --full > "$OUT/${TAG}_${CFG}_bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -c 600 "$OUT/${TAG}_${CFG}_bench.json"
     head -6 "$OUT/${TAG}_${CFG}_kernel_stats.csv"
     exit 0
 fi
@@ -53,5 +53,5 @@ done
 find "$OUT/trace" -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} "$OUT/${TAG}_kernel_stats.csv"
 python3 tools/pmc_summary.py loop_kernel_wv "$OUT/${TAG}_pmc_summary.json" 81920 "$CMD" "$OUT"/pmc_* > /dev/null 2>&1; head -c 1500 "$OUT/${TAG}_pmc_summary.json"
 cp "$OUT/${TAG}_pmc_summary.json" profiles/      # (the bench line last: it cites this summary; its other_configs cite theirs - run the nmpc / enmpc / mhe rounds first)
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -c 900 "$OUT/${TAG}_bench.json"
+timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/${TAG}_bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; tail -c 900 "$OUT/${TAG}_bench.json"
 head -5 "$OUT/${TAG}_kernel_stats.csv"
