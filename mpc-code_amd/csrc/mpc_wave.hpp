@@ -385,6 +385,17 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
     auto mm = [](double a, double b, double c) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0); };
     constexpr int RZ = Cfg::RZ;
     constexpr int SB = (NS + 3) / 4;      // tiles per side of a state matrix
+    // VF: the products of a block as a few asm statements in VGPR form (one-tile stages without the cross term).  This function parks
+    // the iterates in AGPRs, so the compiler selects the AGPR form of the builtin: every result lands in an accumulation register and
+    // is copied out (two v_accvgpr_read) before a VALU, DPP or LDS instruction can touch it, every non-zero srcC is copied in - 23
+    // moves per block of the factorisation, most of them between two dependent products.  Inside an asm statement nothing is padded by
+    // the compiler, so each statement carries the wait states of the DGEMM hazards itself (the counts the compiler pads for the builtin):
+    //   VALU write -> product reads it: 2 (leading s_nop 1);   product -> product reads it as srcA / srcB: 6, as srcC: 4;
+    //   product -> VALU / DPP reads or overwrites it: 6 (trailing s_nop 5);   product -> LDS / memory reads it: 9.
+    // Outputs are early-clobber: a result written by one product of a statement must not share registers with an input of a later one.
+    // The same products on the same operands as the generic path below: not one rounding differs.
+    constexpr bool VF = SB == 1 && !HASM;
+#define MPC_MM "v_mfma_f64_4x4x4_4b_f64 "
     // Everything a pass needs per lane is rebuilt at its start from a lane index the compiler cannot see through: as loop
     // invariants of the iteration loop these registers would stay live across the element-wise phases (and spill there).
     struct TileCtx {
@@ -510,6 +521,64 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             }
             if (more) fetch(d, -PD - d);
             MPC_UNROLL for (int i = 0; i < SB; i++) Pm[i][i] += sz[i];
+            if constexpr (VF) {
+                const double X0i = RE0 + s0, X1i = RE1 + s1, PV0 = HZ[0] + PC[0], Rs = Rr + su;
+                double PB, BtP, PA, psv, X0, X1, Psi;
+                // PB = P B, BtP = B'P, PA = P A, psv = hu + B'(hz + p+);  then X0 / X1 (rows of Lambda) and Psi = B'PA.  PB is read 6 wait
+                // states after it issued (BtP, PA, psv, s_nop 2), PA likewise (psv, s_nop 2, X0, X1).  (NU = 1: X1 is not used.)
+                asm("s_nop 1\n\t"
+                    MPC_MM "%0, %7, %8, 0\n\t"
+                    MPC_MM "%1, %8, %7, 0\n\t"
+                    MPC_MM "%2, %7, %9, 0\n\t"
+                    MPC_MM "%3, %8, %10, %11\n\t"
+                    "s_nop 2\n\t"
+                    MPC_MM "%4, %12, %0, %14\n\t"
+                    MPC_MM "%5, %13, %0, %15\n\t"
+                    MPC_MM "%6, %8, %2, 0\n\t"
+                    "s_nop 5"
+                    : "=&v"(PB), "=&v"(BtP), "=&v"(PA), "=&v"(psv), "=&v"(X0), "=&v"(X1), "=&v"(Psi)
+                    : "v"(Pm[0][0]), "v"(Brl[0]), "v"(Arl[0][0]), "v"(PV0), "v"(HU), "v"(BE0l[0]), "v"(BE1l[0]), "v"(X0i), "v"(X1i));
+                const double a = dpp_move<0x00, 0xF>(X0, X0);
+                double adjm, adjk, det;
+                if (NU == 1) { det = a; adjm = c_1; adjk = k_1; pd_min = dmin(pd_min, a); }
+                else {
+                    const double off = dpp_move<0x55, 0xF>(X0, X0), dd = dpp_move<0x55, 0xF>(X1, X1);
+                    det = __builtin_fma(a, dd, -(off * off));
+                    adjk = __builtin_fma(k_d, dd, __builtin_fma(k_a, a, k_o * off));
+                    adjm = __builtin_fma(c_d, dd, __builtin_fma(c_a, a, c_o * off));
+                    pd_min = dmin(pd_min, dmin(a, det));
+                }
+                // K = (-adj Psi) / det.  The determinant passes through the product's statement, so the reciprocal and its Newton steps
+                // (five dependent VALU instructions, mpc_device.hpp:frcp) are issued behind the product, and the second statement, which
+                // needs their result, behind them: 5 + 2 wait states before anything reads the product.
+                double Kk0;
+                asm("s_nop 1\n\t" MPC_MM "%0, %2, %3, 0" : "=v"(Kk0), "+v"(det) : "v"(adjk), "v"(Psi));
+                const double rdet = frcp(det);
+                asm("s_nop 1" : "+v"(Kk0) : "v"(rdet));
+                Kk0 *= rdet;
+                const double mL = adjm * rdet, mLi = adjk * rdet;
+                // R~ K, Acl = A + B K, Tm = P Acl = PA + PB K, K' hu, kff = -Lambda^-1 psv;  then K' R~ K + Q, Acl' Tm, p = Acl'(hz + p+) + K' hu.
+                // R~ K is read 7 wait states after it issued, Acl 7, Tm 6, K' hu (as srcC) 6; kff goes to LDS 12 wait states after it issued.
+                double RK0, Acl0, Tm0, a2, KFF, acc, acc2, PCn;
+                asm("s_nop 1\n\t"
+                    MPC_MM "%0, %8, %9, 0\n\t"
+                    MPC_MM "%1, %10, %9, %11\n\t"
+                    MPC_MM "%2, %12, %9, %13\n\t"
+                    MPC_MM "%3, %9, %14, 0\n\t"
+                    MPC_MM "%4, %15, %16, 0\n\t"
+                    "s_nop 2\n\t"
+                    MPC_MM "%5, %9, %0, %17\n\t"
+                    MPC_MM "%6, %1, %2, 0\n\t"
+                    MPC_MM "%7, %1, %18, %3\n\t"
+                    "s_nop 5"
+                    : "=&v"(RK0), "=&v"(Acl0), "=&v"(Tm0), "=&v"(a2), "=&v"(KFF), "=&v"(acc), "=&v"(acc2), "=&v"(PCn)
+                    : "v"(Rs), "v"(Kk0), "v"(Btrl[0]), "v"(Arl[0][0]), "v"(BtP), "v"(PA), "v"(HU), "v"(mLi), "v"(psv), "v"(Qr[0][0]), "v"(PV0));
+                q_st[0][-d] = sel_k0 ? Kk0 : (st_l ? mL : KFF);
+                if (NS >= 4) q_sf[-d] = KFF;
+                Pm[0][0] = acc + acc2;      // symmetric up to rounding; the recursion does not amplify the difference
+                PC[0] = PCn;
+                return;
+            }
             // P A, P B, B'P (P symmetric: P' = P)
             double PA[SB][SB], PB[SB], BtP[SB];
             MPC_UNROLL for (int i = 0; i < SB; i++) {
@@ -608,6 +677,26 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             MPC_UNROLL for (int i = 0; i < SB; i++) { Brl[i] = c.Br[i]; Btrl[i] = c.Btr[i]; MPC_UNROLL for (int jj = 0; jj < SB; jj++) Arl[i][jj] = c.Ar[i][jj]; }
             if (LTV) { Arl[0][0] = f[d][NF - 3]; Brl[0] = f[d][NF - 2]; Btrl[0] = f[d][NF - 1]; }
             if (more) fetch(d, -PD - d);
+            if constexpr (VF) {
+                const double PV0 = HZ[0] + PC[0];
+                double Acl0, psv, cst0, KFF, cst, dyn;
+                // Acl = A + B K, psv = hu + B'(hz + p+), K' hu;  then kff = -Lambda^-1 psv, Acl' hz + K' hu, Acl' p+.  psv is read 6 wait states
+                // after it issued (K' hu, s_nop 4), Acl 7, K' hu (as srcC) 6; kff goes to LDS 9 wait states after it issued.
+                asm("s_nop 1\n\t"
+                    MPC_MM "%0, %6, %7, %8\n\t"
+                    MPC_MM "%1, %9, %10, %11\n\t"
+                    MPC_MM "%2, %7, %11, 0\n\t"
+                    "s_nop 4\n\t"
+                    MPC_MM "%3, %12, %1, 0\n\t"
+                    MPC_MM "%4, %0, %13, %2\n\t"
+                    MPC_MM "%5, %0, %14, 0\n\t"
+                    "s_nop 6"
+                    : "=&v"(Acl0), "=&v"(psv), "=&v"(cst0), "=&v"(KFF), "=&v"(cst), "=&v"(dyn)
+                    : "v"(Btrl[0]), "v"(Kk[0]), "v"(Arl[0][0]), "v"(Brl[0]), "v"(PV0), "v"(HU), "v"(mLi), "v"(HZ[0]), "v"(PC[0]));
+                q_st[-d] = KFF;
+                PC[0] = cst + dyn;
+                return;
+            }
             double psv = HU;
             MPC_UNROLL for (int i = 0; i < SB; i++) psv = mm(Brl[i], HZ[i] + PC[i], psv);
             q_st[-d] = mm(mLi, psv, 0.0);
@@ -668,6 +757,22 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             MPC_UNROLL for (int i = 0; i < SB; i++) { Btrl[i] = c.Btr[i]; MPC_UNROLL for (int jj = 0; jj < SB; jj++) Atrl[i][jj] = c.Atr[i][jj]; }
             if (LTV) { Atrl[0][0] = f[d][NF - 2]; Btrl[0] = f[d][NF - 1]; }
             if (more) fetch(d, PD + d);
+            if constexpr (VF) {
+                double Aclt, a0, DUv, DZn0;
+                // Acl' = (A + B K)', B kff, du = K dz + kff;  then dz+ = Acl dz + B kff.  Acl' is read 6 wait states after it issued (B kff, du, s_nop 3).
+                asm("s_nop 1\n\t"
+                    MPC_MM "%0, %4, %5, %6\n\t"
+                    MPC_MM "%1, %5, %7, 0\n\t"
+                    MPC_MM "%2, %8, %9, %7\n\t"
+                    "s_nop 3\n\t"
+                    MPC_MM "%3, %0, %9, %1\n\t"
+                    "s_nop 5"
+                    : "=&v"(Aclt), "=&v"(a0), "=&v"(DUv), "=&v"(DZn0)
+                    : "v"(Kk[0]), "v"(Btrl[0]), "v"(Atrl[0][0]), "v"(KFF), "v"(KkT[0]), "v"(DZ[0]));
+                q_st[0][d] = st_u ? DUv : DZn0;
+                DZ[0] = DZn0;
+                return;
+            }
             double DU = KFF;
             MPC_UNROLL for (int j = 0; j < SB; j++) DU = mm(KkT[j], DZ[j], DU);                      // K dz + kff
             double DZn[SB];
@@ -803,6 +908,7 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         MPC_TSTAMP(6);
     }
 }
+#undef MPC_MM
 
 
 // ------------------------------------------------------------------------------------------------------------------------
