@@ -22,6 +22,7 @@ from . import PKG_DIR
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("MPC_AMD_LIB") or os.path.join(CSRC, "libmpc_amd.so")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"]
+WV_GENERIC_TILES_FLAG = "-DMPC_WV_GENERIC_TILES"      # diagnostic build: the wave kernel's tile sweeps on their generic path (mpc_build_info: ";wv_generic_tiles")
 
 STATUS_SOLVED, STATUS_MAXITER, STATUS_INFEASIBLE = 0, 1, 2
 LOG_NONE, LOG_U, LOG_ALL = 0, 1, 2
@@ -54,8 +55,14 @@ def _dims_key(dims):
     return dims[:7] if len(dims) == 9 and dims[7:] == (0, 0) else dims
 
 
-def jit_library_path(dims) -> str:
-    return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(v) for v in _dims_key(dims)) + ".so")
+def _flags_tag(extra_flags) -> str:
+    """Extra compiler flags as part of a library's file name: "-DMPC_WV_GENERIC_TILES" -> "_MPC_WV_GENERIC_TILES"; none: ""."""
+    import re
+    return "".join("_" + re.sub(r"[^0-9A-Za-z]+", "_", f[2:] if f.startswith("-D") else f).strip("_") for f in extra_flags)
+
+
+def jit_library_path(dims, extra_flags=()) -> str:
+    return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(v) for v in _dims_key(dims)) + _flags_tag(extra_flags) + ".so")
 
 
 def plant_library_path(dims, header_text: str) -> str:
@@ -63,16 +70,21 @@ def plant_library_path(dims, header_text: str) -> str:
     return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(v) for v in _dims_key(dims)) + "_plant_" + hashlib.sha256(header_text.encode()).hexdigest()[:12] + ".so")
 
 
-def build_library(force: bool = False, verbose: bool = False, dims=None, plant_header: Optional[str] = None) -> str:
+def build_library(force: bool = False, verbose: bool = False, dims=None, plant_header: Optional[str] = None, extra_flags=()) -> str:
     """Compile ``csrc/mpc_amd.hip`` for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
     ``dims = (nx, nu, ny, nd, nxp, du_form, general_output_rows[, ss_ineq_rows, ss_eq_rows])`` (the last two: user rows of the
     target problem, zero when left out): a library holding the kernels of exactly that
     dimension set (every kernel is a template on the problem dimensions; the default library carries the sets of the
-    shipped examples, ``mpc_build_info()``), written to ``csrc/jit/`` and reused while the sources are unchanged."""
+    shipped examples, ``mpc_build_info()``), written to ``csrc/jit/`` and reused while the sources are unchanged.
+
+    ``extra_flags``: further compiler flags for a library of one dimension set (a diagnostic build, e.g. ``-DMPC_WV_GENERIC_TILES``); the
+    library's name carries them, so it never stands in for the product's."""
+    extra_flags = tuple(extra_flags)
+    assert not extra_flags or (dims is not None and plant_header is None), "extra flags: a library of one dimension set only"
     srcs = [os.path.join(CSRC, f) for f in ("mpc_amd.hip", "mpc_device.hpp", "mpc_sym.hpp", "mpc_tp.hpp", "mpc_wave.hpp")] + \
            [os.path.join(os.path.dirname(PKG_DIR), "include", "mpc_amd.h")]
-    out = LIB_PATH if dims is None else jit_library_path(dims)
+    out = LIB_PATH if dims is None else jit_library_path(dims, extra_flags)
     hdr = None
     if plant_header is not None:       # the fused closed loop with the Ex-file's own plant function: one library per (dimension set, plant)
         assert dims is not None
@@ -81,7 +93,7 @@ def build_library(force: bool = False, verbose: bool = False, dims=None, plant_h
     if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s)):
         return out
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = list(HIPCC_FLAGS)
+    flags = list(HIPCC_FLAGS) + list(extra_flags)
     if dims is not None:
         os.makedirs(os.path.dirname(out), exist_ok=True)
         flags.append("-DMPC_DIM_LIST(X)=X(" + ",".join(str(v) for v in _dims_key(dims)) + ")")

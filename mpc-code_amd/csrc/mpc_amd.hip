@@ -1980,6 +1980,7 @@ extern "C" const char *mpc_build_info(void)
 #ifdef MPC_NL_PLANT_HEADER
         s += ";nlplant";
 #endif
+        if (mpc::kWvGenericTiles) s += ";wv_generic_tiles";      // -DMPC_WV_GENERIC_TILES (mpc_wave.hpp): a diagnostic build, never the product's
     }
     return s.c_str();
 }

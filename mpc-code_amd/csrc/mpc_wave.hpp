@@ -27,6 +27,14 @@
 
 namespace mpc {
 
+// -DMPC_WV_GENERIC_TILES: the tile sweeps of wv_solve on their generic path at every stage size (the builtin form of the same products):
+// the library tests/test_wv_directions.py compares the product's with, bit for bit.  Never set in a product build.
+#ifdef MPC_WV_GENERIC_TILES
+constexpr bool kWvGenericTiles = true;
+#else
+constexpr bool kWvGenericTiles = false;
+#endif
+
 template <int NS, int NU, int NC, int NI_>
 struct WvCfg {
     static constexpr int NI = NI_;                                     // instances per wave (<= 4 = tiles per matrix-core product)
@@ -394,7 +402,7 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
     //   product -> VALU / DPP reads or overwrites it: 6 (trailing s_nop 5);   product -> LDS / memory reads it: 9.
     // Outputs are early-clobber: a result written by one product of a statement must not share registers with an input of a later one.
     // The same products on the same operands as the generic path below: not one rounding differs.
-    constexpr bool VF = SB == 1 && !HASM;
+    constexpr bool VF = SB == 1 && !HASM && !kWvGenericTiles;
 #define MPC_MM "v_mfma_f64_4x4x4_4b_f64 "
     // Everything a pass needs per lane is rebuilt at its start from a lane index the compiler cannot see through: as loop
     // invariants of the iteration loop these registers would stay live across the element-wise phases (and spill there).
