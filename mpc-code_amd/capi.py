@@ -70,6 +70,19 @@ def plant_library_path(dims, header_text: str) -> str:
     return os.path.join(CSRC, "jit", "libmpc_amd_" + "_".join(str(v) for v in _dims_key(dims)) + "_plant_" + hashlib.sha256(header_text.encode()).hexdigest()[:12] + ".so")
 
 
+def source_files():
+    """Every file a library is compiled from, whichever library: ``csrc/*.hip``, ``csrc/*.hpp`` and the public headers ``include/*.h``
+    (the generated model headers lie under ``csrc/jit/`` and enter a library's name on their own)."""
+    import glob
+    inc = os.path.join(os.path.dirname(PKG_DIR), "include")
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(inc, "*.h")))
+
+
+def library_is_fresh(out: str) -> bool:
+    """A built library that no source file is newer than."""
+    return os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in source_files())
+
+
 def build_library(force: bool = False, verbose: bool = False, dims=None, plant_header: Optional[str] = None, extra_flags=()) -> str:
     """Compile ``csrc/mpc_amd.hip`` for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
@@ -82,15 +95,14 @@ def build_library(force: bool = False, verbose: bool = False, dims=None, plant_h
     library's name carries them, so it never stands in for the product's."""
     extra_flags = tuple(extra_flags)
     assert not extra_flags or (dims is not None and plant_header is None), "extra flags: a library of one dimension set only"
-    srcs = [os.path.join(CSRC, f) for f in ("mpc_amd.hip", "mpc_device.hpp", "mpc_sym.hpp", "mpc_tp.hpp", "mpc_wave.hpp")] + \
-           [os.path.join(os.path.dirname(PKG_DIR), "include", "mpc_amd.h")]
+    src = os.path.join(CSRC, "mpc_amd.hip")
     out = LIB_PATH if dims is None else jit_library_path(dims, extra_flags)
     hdr = None
     if plant_header is not None:       # the fused closed loop with the Ex-file's own plant function: one library per (dimension set, plant)
         assert dims is not None
         out = plant_library_path(dims, plant_header)
         hdr = out[:-3] + "_model.hpp"
-    if not force and os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs if os.path.exists(s)):
+    if not force and library_is_fresh(out):
         return out
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     flags = list(HIPCC_FLAGS) + list(extra_flags)
@@ -108,7 +120,7 @@ def build_library(force: bool = False, verbose: bool = False, dims=None, plant_h
         from concurrent.futures import ThreadPoolExecutor
         cflags = [f for f in flags if f != "-shared"]
         objs = [tmp + ".a.o", tmp + ".b.o"]
-        cmds = [[hipcc] + cflags + ["-DMPC_HAVE_PART2", "-c", "-o", objs[0], srcs[0]], [hipcc] + cflags + ["-DMPC_PART2", "-c", "-o", objs[1], srcs[0]]]
+        cmds = [[hipcc] + cflags + ["-DMPC_HAVE_PART2", "-c", "-o", objs[0], src], [hipcc] + cflags + ["-DMPC_PART2", "-c", "-o", objs[1], src]]
         if verbose:
             for c in cmds:
                 print(" ".join(c))
@@ -123,7 +135,7 @@ def build_library(force: bool = False, verbose: bool = False, dims=None, plant_h
                     os.remove(o)
         os.replace(tmp, out)
         return out
-    cmd = [hipcc] + flags + ["-o", tmp, srcs[0]]
+    cmd = [hipcc] + flags + ["-o", tmp, src]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)

@@ -17,38 +17,16 @@
 #endif
 
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <dlfcn.h>
-#include <unistd.h>
+#include "mpc_comm.hpp"      // (with mpc_host.hpp: error state, DevBuf, the SoA staging, the log table)
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 using namespace mpc;
-
-// ---------------------------------------------------------------------------------------------------
-// error handling
-// ---------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-static int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define HIP_TRY(x)                                                                                       \
-    do {                                                                                                 \
-        hipError_t e_ = (x);                                                                             \
-        if (e_ != hipSuccess) return fail(-10, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
 
 #ifndef MPC_PART2
 extern "C" const char *mpc_last_error(void) { return g_err; }
@@ -1565,20 +1543,6 @@ extern "C" int mpc_part2_launchers(int nx, int nu, int ny, int nd, int nxp, int 
 extern "C" int mpc_part2_launchers(int nx, int nu, int ny, int nd, int nxp, int du, int ng, int ngs, int nhs, int mode, void *out);
 #endif
 
-struct DevBuf {
-    void *p = nullptr; size_t bytes = 0;
-    int ensure(size_t n)
-    {
-        if (n <= bytes) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        HIP_TRY(hipMalloc(&p, n));
-        bytes = n;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
 struct mpc_handle {
     DevProblem hp;              // host copy
     DevProblem *dp = nullptr;   // device copy
@@ -1605,31 +1569,10 @@ struct mpc_handle {
     DevBuf soft_ws, soft_sl, soft_keep; int soft_B = 0;      // soft output constraints: the arrowhead solver's workspace, the last call's optimal slacks
     DevBuf pxy_in, pxy_lin, pxy_ws, off_px, off_py; int off_B = 0; bool off_has_px = false, off_has_py = false;
     DevBuf msch; int msch_steps = 0; bool msch_px = false, msch_py = false;      // def_px / def_py over the horizon for every step of the fused loop
-    DevBuf st_x, st_xhat, st_dhat, st_P, st_u, st_xs, st_us, st_flag, st_Kg, st_Pn, st_tw, sch, logs, logi;
-    std::map<std::string, std::pair<size_t, int>> log_off;   // name -> (offset in doubles / ints, dim)
-    // multi-GPU (one process per GPU): RCCL communicator over the ranks of the job, staging buffers of the collectives
-    ncclComm_t comm = nullptr; int rank = 0, world = 1;
-    DevBuf coll_send, coll_recv;
+    DevBuf st_x, st_xhat, st_dhat, st_P, st_u, st_xs, st_us, st_flag, st_Kg, st_Pn, st_tw, sch;
+    LogTab log;                 // the logs mpc_loop_alloc enabled
+    mpc_comm::State comm;       // multi-GPU (one process per GPU): the ranks of the job, staging buffers of the collectives
 };
-
-static size_t pad64(size_t b) { return (b + 63) / 64 * 64; }
-
-// host [B][d] -> SoA staging [d][Bs]
-static void to_soa(const double *src, int B, int d, size_t Bs, double *dst)
-{
-    for (int i = 0; i < d; i++) {
-        double *row = dst + (size_t)i * Bs;
-        for (int b = 0; b < B; b++) row[b] = src[(size_t)b * d + i];
-        for (size_t b = B; b < Bs; b++) row[b] = 0.0;
-    }
-}
-static void from_soa(const double *src, int B, int d, size_t Bs, double *dst)
-{
-    for (int i = 0; i < d; i++) {
-        const double *row = src + (size_t)i * Bs;
-        for (int b = 0; b < B; b++) dst[(size_t)b * d + i] = row[b];
-    }
-}
 
 // rows carried as stage states of their own: bounded output rows that are not a multiple of one state (rows[] (optional) receives their indices), then the user
 // inequality rows (rows[] = -1)
@@ -1943,19 +1886,17 @@ extern "C" int mpc_lin_create(const mpc_lin_desc *d, mpc_handle **out)
     return 0;
 }
 
-extern "C" int mpc_comm_destroy(mpc_handle *h);
-
 extern "C" void mpc_destroy(mpc_handle *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    (void)mpc_comm_destroy(h);
-    h->coll_send.release(); h->coll_recv.release();
+    mpc_comm::destroy(h->comm, h->device, h->stream);
+    h->log.release();
     h->pc_prev.release(); h->pc_valid.release(); h->pc_guess.release(); h->pc_traj.release();
     h->soft_ws.release(); h->soft_sl.release(); h->soft_keep.release();
     h->pxy_in.release(); h->pxy_lin.release(); h->pxy_ws.release(); h->off_px.release(); h->off_py.release(); h->msch.release();
-    for (DevBuf *b : {&h->scratch, &h->ws, &h->st_x, &h->st_xhat, &h->st_dhat, &h->st_P, &h->st_u, &h->st_xs, &h->st_us, &h->st_flag, &h->st_Kg, &h->st_Pn, &h->st_tw, &h->sch, &h->logs, &h->logi}) b->release();
+    for (DevBuf *b : {&h->scratch, &h->ws, &h->st_x, &h->st_xhat, &h->st_dhat, &h->st_P, &h->st_u, &h->st_xs, &h->st_us, &h->st_flag, &h->st_Kg, &h->st_Pn, &h->st_tw, &h->sch}) b->release();
     if (h->dp) (void)hipFree(h->dp);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -2381,24 +2322,20 @@ extern "C" int mpc_loop_alloc(mpc_handle *h, int32_t B, int32_t max_steps, int32
     if (ensure_ws(h, Bs)) return -10;
     const int sdim = P.ny + P.nu + P.nxp + P.ny;   // ysp usp pxp pyp
     if (h->sch.ensure((size_t)max_steps * sdim * 8)) return -10;
-    h->log_off.clear();
-    size_t off = 0;
+    std::vector<std::pair<const char *, int>> dlogs;
     const int dims[] = {P.nu, P.nx, P.nx, P.nu, P.ny, P.nxp, P.nd};
     for (int i = 0; i < 7; i++) {
         const bool on = log_level >= MPC_LOG_ALL || (log_level >= MPC_LOG_U && i == 0);
-        if (on && dims[i] > 0) { h->log_off[kLogD[i]] = {off, dims[i]}; off += (size_t)max_steps * dims[i] * Bs; }
+        if (on && dims[i] > 0) dlogs.push_back({kLogD[i], dims[i]});
     }
     if (P.soft) {      // soft output constraints: the optimal slack vector of every step (log "SL", with the inputs), and the arrowhead solver's workspace
-        if (log_level >= MPC_LOG_U) { h->log_off["SL"] = {off, 2 * P.ny}; off += (size_t)max_steps * 2 * P.ny * Bs; }
+        if (log_level >= MPC_LOG_U) dlogs.push_back({"SL", 2 * P.ny});
         if (h->soft_ws.ensure((size_t)(Bs / 64) * h->L.soft_fields * P.N * 64 * sizeof(double)) || h->soft_keep.ensure((size_t)2 * P.ny * Bs * sizeof(double))) return -10;
         HIP_TRY(hipMemsetAsync(h->soft_keep.p, 0, h->soft_keep.bytes, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    if (h->logs.ensure(off ? off * 8 : 8)) return -10;
-    if (log_level >= MPC_LOG_U) {
-        for (int i = 0; i < 4; i++) h->log_off[kLogI[i]] = {(size_t)i * max_steps * Bs, 0};
-        if (h->logi.ensure((size_t)4 * max_steps * Bs * 4)) return -10;
-    }
+    h->log.layout(dlogs, log_level >= MPC_LOG_U ? std::vector<const char *>(kLogI, kLogI + 4) : std::vector<const char *>(), max_steps, Bs);
+    if (h->log.alloc()) return -10;
     h->B = B; h->Bs = Bs; h->max_steps = max_steps; h->log_level = log_level; h->sched_steps = 0;
     return 0;
 }
@@ -2550,16 +2487,10 @@ extern "C" int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps)
         a.u = (double *)h->st_u.p; a.xs = (double *)h->st_xs.p; a.us = (double *)h->st_us.p;
         a.ysp = sch + (size_t)k * P.ny; a.usp = sch + ms * P.ny + (size_t)k * P.nu;
         a.pxp = sch + ms * (P.ny + P.nu) + (size_t)k * P.nxp; a.pyp = sch + ms * (P.ny + P.nu + P.nxp) + (size_t)k * P.ny;
-        auto dl = [&](const char *nm) -> double * {
-            auto it = h->log_off.find(nm);
-            if (it == h->log_off.end()) return nullptr;
-            return (double *)h->logs.p + it->second.first + (size_t)k * it->second.second * Bs;
-        };
+        auto dl = [&](const char *nm) -> double * { return (double *)h->log.dev(nm, k); };      // (nullptr: a log that is not enabled)
+        auto il = [&](const char *nm) -> int32_t * { return (int32_t *)h->log.dev(nm, k); };
         a.U = dl("U"); a.XHAT = dl("X_HAT"); a.XS = dl("XS"); a.US = dl("US"); a.YS = dl("YS"); a.XP = dl("Xp"); a.DHAT = dl("D_HAT");
-        if (h->log_level >= MPC_LOG_U) {
-            int32_t *li = (int32_t *)h->logi.p;
-            a.st_dyn = li + (size_t)k * Bs; a.st_ss = li + ms * Bs + (size_t)k * Bs; a.it_dyn = li + 2 * ms * Bs + (size_t)k * Bs; a.it_ss = li + 3 * ms * Bs + (size_t)k * Bs;
-        } else a.st_dyn = a.st_ss = a.it_dyn = a.it_ss = nullptr;
+        a.st_dyn = il("STATUS_DYN"); a.st_ss = il("STATUS_SS"); a.it_dyn = il("ITERS_DYN"); a.it_ss = il("ITERS_SS");
         a.ws_valid = (int32_t *)h->st_flag.p; a.kf_valid = a.ws_valid + Bs; a.Kg = (double *)h->st_Kg.p; a.Pn = (double *)h->st_Pn.p;
         a.tw = (double *)h->st_tw.p; a.tw_valid = a.ws_valid + 2 * Bs;
         a.ws = (double *)h->ws.p; a.B = h->B; a.nsteps = n; a.Bs = Bs; a.N = P.N;
@@ -2595,24 +2526,11 @@ extern "C" int mpc_loop_sync(mpc_handle *h)
 extern "C" int mpc_loop_get_log(mpc_handle *h, const char *name, void *out)
 {
     if (!h || !name || !out) return fail(-1, "null argument");
-    auto it = h->log_off.find(name);
-    if (it == h->log_off.end()) return fail(-8, "log '%s' was not enabled in mpc_loop_alloc", name);
+    const LogTab::Entry *e = h->log.find(name);
+    if (!e) return fail(-8, "log '%s' was not enabled in mpc_loop_alloc", name);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t Bs = h->Bs; const int B = h->B, ns = h->sched_steps;
-    if (it->second.second > 0) {
-        const int d = it->second.second;
-        std::vector<double> st((size_t)ns * d * Bs);
-        HIP_TRY(hipMemcpy(st.data(), (double *)h->logs.p + it->second.first, st.size() * 8, hipMemcpyDeviceToHost));
-        double *o = (double *)out;
-        for (int k = 0; k < ns; k++) from_soa(st.data() + (size_t)k * d * Bs, B, d, Bs, o + (size_t)k * B * d);
-    } else {
-        std::vector<int32_t> st((size_t)ns * Bs);
-        HIP_TRY(hipMemcpy(st.data(), (int32_t *)h->logi.p + it->second.first, st.size() * 4, hipMemcpyDeviceToHost));
-        int32_t *o = (int32_t *)out;
-        for (int k = 0; k < ns; k++) for (int b = 0; b < B; b++) o[(size_t)k * B + b] = st[(size_t)k * Bs + b];
-    }
-    return 0;
+    return h->log.read(*e, h->sched_steps, h->B, out);
 }
 
 extern "C" void *mpc_dev_ptr(mpc_handle *h, const char *name, int64_t *bpad)
@@ -2627,11 +2545,8 @@ extern "C" void *mpc_dev_ptr(mpc_handle *h, const char *name, int64_t *bpad)
     if (n == "u") return h->st_u.p;
     if (n == "xs") return h->st_xs.p;
     if (n == "us") return h->st_us.p;
-    if (n == "coll_recv") return h->coll_recv.p;
-    auto it = h->log_off.find(n);
-    if (it == h->log_off.end()) return nullptr;
-    if (it->second.second > 0) return (double *)h->logs.p + it->second.first;
-    return (int32_t *)h->logi.p + it->second.first;
+    if (n == "coll_recv") return h->comm.recv.p;
+    return h->log.dev(name);
 }
 
 extern "C" int mpc_pack_u(mpc_handle *h, void *dst_dev)
@@ -2644,136 +2559,18 @@ extern "C" int mpc_pack_u(mpc_handle *h, void *dst_dev)
 }
 
 // ---------------------------------------------------------------------------------------------------
-// multi-GPU: one process per GPU, RCCL over xGMI.  Instances are independent, so the only
-// exchanges are the all-gather of the controls (per step: mpc_allgather_u; per run: mpc_allgather_log) and the
-// job-level barrier / reductions of the benchmark harness.  librccl is opened on first use: a single-GPU user of
-// the library never loads it.
+// multi-GPU: one process per GPU, RCCL over xGMI (the collective itself: mpc_comm.hpp).  Instances are
+// independent, so the only exchanges are the all-gather of the controls (per step: mpc_allgather_u; per run: mpc_allgather_log)
+// and the job-level barrier / reductions of the benchmark harness.
 // ---------------------------------------------------------------------------------------------------
-namespace {
-struct Rccl {
-    void *lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-};
-Rccl g_rccl;
-int rccl_load()
-{
-    if (g_rccl.lib) return 0;
-    const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-    void *lib = nullptr;
-    for (const char *n : names) { lib = dlopen(n, RTLD_NOW | RTLD_LOCAL); if (lib) break; }
-    if (!lib) return fail(-12, "librccl.so not found: %s", dlerror());
-#define MPC_RCCL_SYM(field, sym) *(void **)(&g_rccl.field) = dlsym(lib, sym); if (!g_rccl.field) { dlclose(lib); return fail(-12, "librccl lacks %s", sym); }
-    MPC_RCCL_SYM(GetUniqueId, "ncclGetUniqueId") MPC_RCCL_SYM(CommInitRank, "ncclCommInitRank") MPC_RCCL_SYM(CommDestroy, "ncclCommDestroy")
-    MPC_RCCL_SYM(AllGather, "ncclAllGather") MPC_RCCL_SYM(AllReduce, "ncclAllReduce") MPC_RCCL_SYM(GetErrorString, "ncclGetErrorString")
-#undef MPC_RCCL_SYM
-    g_rccl.lib = lib;
-    return 0;
-}
-}  // namespace
-#define RCCL_TRY(x)                                                                                      \
-    do {                                                                                                 \
-        ncclResult_t r_ = (x);                                                                           \
-        if (r_ != ncclSuccess) return fail(-12, "%s failed: %s (%s:%d)", #x, g_rccl.GetErrorString(r_), __FILE__, __LINE__); \
-    } while (0)
-
-// RCCL writes its version banner to stdout when it initialises (NCCL_DEBUG=VERSION, as on the benchmark boxes): while one of its set-up
-// calls runs, file descriptor 1 points at stderr, so that a caller's stdout carries only what the caller prints (bench.py: one JSON line).
-namespace {
-struct StdoutToStderr {
-    int saved = -1;
-    StdoutToStderr() { fflush(stdout); saved = dup(1); if (saved >= 0) (void)dup2(2, 1); }
-    ~StdoutToStderr() { fflush(stdout); if (saved >= 0) { (void)dup2(saved, 1); close(saved); } }
-};
-}
-
-extern "C" int mpc_comm_unique_id(char *out128)
-{
-    if (!out128) return fail(-1, "null argument");
-    if (rccl_load()) return -12;
-    ncclUniqueId id;
-    StdoutToStderr quiet;
-    RCCL_TRY(g_rccl.GetUniqueId(&id));
-    static_assert(sizeof(id) == MPC_COMM_ID_BYTES, "ncclUniqueId size");
-    std::memcpy(out128, &id, sizeof(id));
-    return 0;
-}
-
-extern "C" int mpc_comm_init(mpc_handle *h, int32_t rank, int32_t world, const char *id128)
-{
-    if (!h || !id128 || world < 1 || rank < 0 || rank >= world) return fail(-1, "bad argument");
-    if (h->comm) return fail(-1, "the handle already has a communicator");
-    if (rccl_load()) return -12;
-    HIP_TRY(hipSetDevice(h->device));
-    ncclUniqueId id;
-    std::memcpy(&id, id128, sizeof(id));
-    {
-        StdoutToStderr quiet;
-        RCCL_TRY(g_rccl.CommInitRank(&h->comm, world, id, rank));
-    }
-    h->rank = rank; h->world = world;
-    return 0;
-}
-
-extern "C" int mpc_comm_destroy(mpc_handle *h)
-{
-    if (!h || !h->comm) return 0;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    g_rccl.CommDestroy(h->comm);
-    h->comm = nullptr; h->rank = 0; h->world = 1;
-    return 0;
-}
-
-extern "C" int mpc_comm_rank(mpc_handle *h, int32_t *rank, int32_t *world)
-{
-    if (!h) return fail(-1, "null handle");
-    if (rank) *rank = h->rank;
-    if (world) *world = h->world;
-    return 0;
-}
-
-// all-gather of `bytes` bytes per rank between host buffers, staged through device memory (rank r's block lands at recv + r * bytes)
-extern "C" int mpc_comm_allgather(mpc_handle *h, const void *send, size_t bytes, void *recv)
-{
-    if (!h || !send || !recv || bytes == 0) return fail(-1, "bad argument");
-    if (!h->comm) { std::memcpy(recv, send, bytes); return 0; }
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->coll_send.ensure(bytes) || h->coll_recv.ensure(bytes * h->world)) return -10;
-    HIP_TRY(hipMemcpyAsync(h->coll_send.p, send, bytes, hipMemcpyHostToDevice, h->stream));
-    RCCL_TRY(g_rccl.AllGather(h->coll_send.p, h->coll_recv.p, bytes, ncclChar, h->comm, h->stream));
-    HIP_TRY(hipMemcpyAsync(recv, h->coll_recv.p, bytes * h->world, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// max over the ranks of n host doubles, in place
-extern "C" int mpc_comm_allreduce_max(mpc_handle *h, double *inout, int32_t n)
-{
-    if (!h || !inout || n < 1) return fail(-1, "bad argument");
-    if (!h->comm) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->coll_send.ensure(sizeof(double) * n)) return -10;
-    HIP_TRY(hipMemcpyAsync(h->coll_send.p, inout, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
-    RCCL_TRY(g_rccl.AllReduce(h->coll_send.p, h->coll_send.p, n, ncclDouble, ncclMax, h->comm, h->stream));
-    HIP_TRY(hipMemcpyAsync(inout, h->coll_send.p, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// everything queued on this handle's stream on every rank has completed when this returns
-extern "C" int mpc_comm_barrier(mpc_handle *h)
-{
-    if (!h) return fail(-1, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->comm) { double one = 1.0; const int rc = mpc_comm_allreduce_max(h, &one, 1); if (rc) return rc; }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
-}
+static_assert(MPC_COMM_ID_BYTES == mpc_comm::kIdBytes, "ncclUniqueId size");
+extern "C" int mpc_comm_unique_id(char *out128) { return mpc_comm::unique_id(out128); }
+extern "C" int mpc_comm_init(mpc_handle *h, int32_t rank, int32_t world, const char *id128) { return h ? mpc_comm::init(h->comm, h->device, rank, world, id128) : fail(-1, "bad argument"); }
+extern "C" int mpc_comm_destroy(mpc_handle *h) { if (h) mpc_comm::destroy(h->comm, h->device, h->stream); return 0; }
+extern "C" int mpc_comm_rank(mpc_handle *h, int32_t *rank, int32_t *world) { if (!h) return fail(-1, "null handle"); if (rank) *rank = h->comm.rank; if (world) *world = h->comm.world; return 0; }
+extern "C" int mpc_comm_allgather(mpc_handle *h, const void *send, size_t bytes, void *recv) { return h ? mpc_comm::allgather_host(h->comm, h->device, h->stream, send, bytes, recv) : fail(-1, "bad argument"); }
+extern "C" int mpc_comm_allreduce_max(mpc_handle *h, double *inout, int32_t n) { return h ? mpc_comm::allreduce_max(h->comm, h->device, h->stream, inout, n) : fail(-1, "bad argument"); }
+extern "C" int mpc_comm_barrier(mpc_handle *h) { return h ? mpc_comm::barrier(h->comm, h->device, h->stream) : fail(-1, "null handle"); }
 
 // u* of the last closed-loop step of every rank: ncclAllGather(u_local[B][nu]).  u_all (host, optional)
 // receives [world][B][nu]; the gathered block also stays on the device (mpc_dev_ptr "coll_recv").
@@ -2782,12 +2579,12 @@ extern "C" int mpc_allgather_u(mpc_handle *h, double *u_all)
     if (!h || h->B == 0) return fail(-1, "mpc_loop_alloc first");
     HIP_TRY(hipSetDevice(h->device));
     const size_t n = (size_t)h->B * h->hp.nu, bytes = n * sizeof(double);
-    if (h->coll_send.ensure(bytes) || h->coll_recv.ensure(bytes * h->world)) return -10;
-    hipLaunchKernelGGL(pack_u_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, (const double *)h->st_u.p, (double *)h->coll_send.p, h->B, h->Bs, h->hp.nu);
+    if (int rc = mpc_comm::agree_count(h->comm, h->device, h->stream, n)) return rc;      // (before the pack: the check stages through comm.send)
+    if (h->comm.send.ensure(bytes)) return -10;
+    hipLaunchKernelGGL(pack_u_kernel, dim3((h->B + 255) / 256), dim3(256), 0, h->stream, (const double *)h->st_u.p, (double *)h->comm.send.p, h->B, h->Bs, h->hp.nu);
     HIP_TRY(hipGetLastError());
-    if (h->comm) RCCL_TRY(g_rccl.AllGather(h->coll_send.p, h->coll_recv.p, n, ncclDouble, h->comm, h->stream));
-    else HIP_TRY(hipMemcpyAsync(h->coll_recv.p, h->coll_send.p, bytes, hipMemcpyDeviceToDevice, h->stream));
-    if (u_all) { HIP_TRY(hipMemcpyAsync(u_all, h->coll_recv.p, bytes * h->world, hipMemcpyDeviceToHost, h->stream)); HIP_TRY(hipStreamSynchronize(h->stream)); }
+    if (int rc = mpc_comm::allgather_dev(h->comm, h->device, h->stream, (const double *)h->comm.send.p, n)) return rc;
+    if (u_all) { HIP_TRY(hipMemcpyAsync(u_all, h->comm.recv.p, bytes * h->comm.world, hipMemcpyDeviceToHost, h->stream)); HIP_TRY(hipStreamSynchronize(h->stream)); }
     return 0;
 }
 
@@ -2796,45 +2593,33 @@ extern "C" int mpc_allgather_u(mpc_handle *h, double *u_all)
 extern "C" int mpc_allgather_log(mpc_handle *h, const char *name, int32_t k0, int32_t nsteps, double *out)
 {
     if (!h || h->B == 0 || !name) return fail(-1, "bad argument");
-    auto it = h->log_off.find(name);
-    if (it == h->log_off.end() || it->second.second == 0) return fail(-8, "float64 log '%s' was not enabled in mpc_loop_alloc", name);
-    if (k0 < 0 || nsteps < 1 || k0 + nsteps > h->max_steps) return fail(-1, "steps out of range");
-    HIP_TRY(hipSetDevice(h->device));
-    const int d = it->second.second;
-    const size_t row = (size_t)d * h->Bs, n = (size_t)nsteps * row;
-    if (h->coll_recv.ensure(n * sizeof(double) * h->world)) return -10;
-    const double *src = (const double *)h->logs.p + it->second.first + (size_t)k0 * row;
-    if (h->comm) RCCL_TRY(g_rccl.AllGather(src, h->coll_recv.p, n, ncclDouble, h->comm, h->stream));
-    else HIP_TRY(hipMemcpyAsync(h->coll_recv.p, src, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    const LogTab::Entry *e = h->log.find(name);
+    if (!e || e->dim == 0) return fail(-8, "float64 log '%s' was not enabled in mpc_loop_alloc", name);
+    const double *src; size_t n;
+    if (int rc = h->log.slice(*e, k0, nsteps, &src, &n)) return rc;
+    if (int rc = mpc_comm::allgather_dev(h->comm, h->device, h->stream, src, n)) return rc;
     if (out) {
-        std::vector<double> st(n * h->world);
-        HIP_TRY(hipMemcpyAsync(st.data(), h->coll_recv.p, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        std::vector<double> st(n * h->comm.world);
+        HIP_TRY(hipMemcpyAsync(st.data(), h->comm.recv.p, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        for (int r = 0; r < h->world; r++)
-            for (int k = 0; k < nsteps; k++)
-                from_soa(st.data() + ((size_t)r * nsteps + k) * row, h->B, d, h->Bs, out + (((size_t)r * nsteps + k) * h->B) * d);
+        LogTab::unpad(st.data(), (size_t)h->comm.world * nsteps, e->dim, h->B, h->Bs, out);
     }
     return 0;
 }
 
 #ifdef MPC_STAMPS   /* diagnostic build only, see tools/stamps.py */
-extern "C" int mpc_debug_stamps(unsigned long long *out, int n, int reset)
-{
-    if (out) { if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mpc::mpc_stamp_buf), sizeof(unsigned long long) * n) != hipSuccess) return -1; }
-    if (reset) { static unsigned long long z[4096 * 8]; if (hipMemcpyToSymbol(HIP_SYMBOL(mpc::mpc_stamp_buf), z, sizeof(z)) != hipSuccess) return -1; }
-    return 0;
-}
+extern "C" int mpc_debug_stamps(unsigned long long *out, int n, int reset) { return debug_stamps(mpc::mpc_stamp_buf, out, n, reset); }
 #endif
 
 extern "C" int mpc_pack_log(mpc_handle *h, const char *name, int32_t k0, int32_t nsteps, void *dst_dev)
 {
     if (!h || h->B == 0 || !name || !dst_dev) return fail(-1, "bad argument");
-    auto it = h->log_off.find(name);
-    if (it == h->log_off.end() || it->second.second == 0) return fail(-8, "float64 log '%s' was not enabled in mpc_loop_alloc", name);
-    if (k0 < 0 || nsteps < 1 || k0 + nsteps > h->max_steps) return fail(-1, "steps out of range");
+    const LogTab::Entry *e = h->log.find(name);
+    if (!e || e->dim == 0) return fail(-8, "float64 log '%s' was not enabled in mpc_loop_alloc", name);
+    const double *src; size_t n;
+    if (int rc = h->log.slice(*e, k0, nsteps, &src, &n)) return rc;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t row = (size_t)it->second.second * h->Bs;
-    HIP_TRY(hipMemcpyAsync(dst_dev, (double *)h->logs.p + it->second.first + (size_t)k0 * row, (size_t)nsteps * row * 8, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dst_dev, src, n * 8, hipMemcpyDeviceToDevice, h->stream));
     return 0;
 }
 

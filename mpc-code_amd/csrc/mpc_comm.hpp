@@ -1,9 +1,9 @@
-// Multi-GPU collective of the per-model libraries (libmpc_enmpc_<model>.so): one process per GPU, RCCL over xGMI, as
-// libmpc_amd.so has it for the linear path (mpc_amd.hip: mpc_comm_*).  Instances are independent, so the only exchanges are the all-gather of the
-// controls - straight from the device log, device to device - and the job-level barrier / reductions of a harness.  librccl is opened on first
-// use: a single-GPU user of the library never loads it.  The including .hip defines fail(code, fmt, ...) and HIP_TRY.
+// Multi-GPU collective of libmpc_amd.so (mpc_comm_*) and of the per-model libraries libmpc_enmpc_<model>.so (enmpc_comm_*): one process per GPU,
+// RCCL over xGMI.  Instances are independent, so the only exchanges are the all-gather of the controls - straight from
+// the device log, device to device - and the job-level barrier / reductions of a harness.  librccl is opened on first use: a single-GPU user
+// of a library never loads it.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "mpc_host.hpp"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <unistd.h>
@@ -53,16 +53,10 @@ struct StdoutToStderr {
     ~StdoutToStderr() { fflush(stdout); if (saved >= 0) { (void)dup2(saved, 1); close(saved); } }
 };
 
-struct Buf {
-    void *p = nullptr; size_t bytes = 0;
-    int ensure(size_t n) { if (n <= bytes) return 0; if (p) (void)hipFree(p); p = nullptr; bytes = 0; HIP_TRY(hipMalloc(&p, n)); bytes = n; return 0; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-
 // the communicator of one handle: the ranks of the job, this rank's staging buffers
 struct State {
     ncclComm_t comm = nullptr; int rank = 0, world = 1;
-    Buf send, recv;
+    DevBuf send, recv;
     size_t agreed_n = 0;      // the per-rank count of allgather_dev every rank was last seen to agree on
 };
 
@@ -132,19 +126,25 @@ static int barrier(State &c, int device, hipStream_t stream)
     HIP_TRY(hipStreamSynchronize(stream));
     return 0;
 }
+// every rank brings the same count n to an all-gather of doubles (ncclAllGather wants that: unequal shards hang or corrupt the gather): checked
+// once per count with a small gather of its own, which goes through c.send and c.recv
+static int agree_count(State &c, int device, hipStream_t stream, size_t n)
+{
+    if (!c.comm || c.world < 2 || c.agreed_n == n) return 0;
+    unsigned long long mine = n, all[64];
+    if (c.world > 64) return fail(-1, "more than 64 ranks");
+    if (int rc = allgather_host(c, device, stream, &mine, sizeof(mine), all)) return rc;
+    for (int r = 0; r < c.world; r++)
+        if (all[r] != mine) return fail(-1, "all-gather of a log: rank %d holds %llu doubles per rank, rank %d holds %llu - every rank must allocate the same batch and step count (pad the shards: shard.py)", c.rank, mine, r, all[r]);
+    c.agreed_n = n;
+    return 0;
+}
 // n doubles per rank from device memory `src` into c.recv ([world][n], device), asynchronous on `stream`: the single RCCL all-gather of the controls
+// (src may be c.send once agree_count has seen n: the check then leaves the staging buffers alone)
 static int allgather_dev(State &c, int device, hipStream_t stream, const double *src, size_t n)
 {
     HIP_TRY(hipSetDevice(device));
-    if (c.comm && c.world > 1 && c.agreed_n != n) {
-        // ncclAllGather wants the same count on every rank (unequal shards hang or corrupt the gather): checked once per count with a small gather of its own
-        unsigned long long mine = n, all[64];
-        if (c.world > 64) return fail(-1, "more than 64 ranks");
-        if (int rc = allgather_host(c, device, stream, &mine, sizeof(mine), all)) return rc;
-        for (int r = 0; r < c.world; r++)
-            if (all[r] != mine) return fail(-1, "all-gather of a log: rank %d holds %llu doubles per rank, rank %d holds %llu - every rank must allocate the same batch and step count (pad the shards: shard.py)", c.rank, mine, r, all[r]);
-        c.agreed_n = n;
-    }
+    if (int rc = agree_count(c, device, stream, n)) return rc;
     if (c.recv.ensure(n * sizeof(double) * c.world)) return -10;
     if (c.comm) MPC_RCCL_TRY(g_rccl.AllGather(src, c.recv.p, n, ncclDouble, c.comm, stream));
     else HIP_TRY(hipMemcpyAsync(c.recv.p, src, n * sizeof(double), hipMemcpyDeviceToDevice, stream));

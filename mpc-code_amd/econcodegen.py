@@ -25,6 +25,7 @@ import numpy as np
 
 from . import PKG_DIR
 from . import symtrace as st
+from .capi import source_files
 
 CSRC = os.path.join(PKG_DIR, "csrc")
 # -amdgpu-spill-vgpr-to-agpr=0: a code-generator fault of this toolchain (AMD clang 22.0.0git, roc-7.2.0), found in round 5 in enmpc_mhe_kernel<64>: with that option on (the
@@ -231,11 +232,9 @@ struct EcModel {{
 
 
 def enmpc_library_path(header_text: str) -> str:
-    inc = os.path.join(os.path.dirname(PKG_DIR), "include")
-    srcs = [os.path.join(CSRC, f) for f in ("mpc_enmpc.hip", "mpc_enmpc.hpp", "mpc_rk4s2.hpp", "mpc_device.hpp", "mpc_sym.hpp", "mpc_tp.hpp", "mpc_comm.hpp")] + [os.path.join(inc, "mpc_enmpc.h")]
     hsh = hashlib.sha256(header_text.encode())
     hsh.update(" ".join(ENMPC_FLAGS).encode())
-    for s in srcs:
+    for s in source_files():
         hsh.update(open(s, "rb").read())
     return os.path.join(CSRC, "jit", f"libmpc_enmpc_{hsh.hexdigest()[:16]}.so")
 

@@ -79,5 +79,15 @@ def test_product_and_bench_do_not_use_pytorch():
     for f in files:
         src = open(f, errors="ignore").read()
         assert not re.search(r"^\s*(from|import)\s+torch", src, re.M), f
-    hip = open(os.path.join(ROOT, "mpc-code_amd", "csrc", "mpc_amd.hip")).read()
-    assert "ncclAllGather" in hip and "ncclCommInitRank" in hip
+    csrc = os.path.join(ROOT, "mpc-code_amd", "csrc")
+    assert '#include "mpc_comm.hpp"' in open(os.path.join(csrc, "mpc_amd.hip")).read()
+    comm = open(os.path.join(csrc, "mpc_comm.hpp")).read()
+    assert "ncclAllGather" in comm and "ncclCommInitRank" in comm
+    # ... and in the built library: the names it looks up in librccl, which it opens on first use and does not link
+    import subprocess
+    from mpc_code_amd import capi
+    lib = capi.build_library()
+    blob = open(lib, "rb").read()
+    assert b"ncclAllGather\0" in blob and b"ncclCommInitRank\0" in blob
+    dyn = subprocess.run(["readelf", "-d", lib], check=True, capture_output=True, text=True).stdout
+    assert "NEEDED" in dyn and "librccl" not in dyn, dyn

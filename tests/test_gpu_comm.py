@@ -51,6 +51,32 @@ def test_single_rank_communicator_gathers_what_the_kernel_logged_and_keeps_stdou
         s.close()
 
 
+def test_linear_gathers_reuse_the_staging_buffer_across_counts_at_a_padded_batch(pkg):
+    """B = 65 (rows of 128 on the device) and a one-rank communicator: a gather of three steps, then a smaller count into the same (larger) buffer, then
+    the packed u*, then the first count again - each equal to the matching slice of the log the host reads."""
+    from mpc_code_amd import capi
+    p = pkg.load_problem(pkg.example_path("cstr_lmpc.py"))
+    s = capi.Solver(p, device=0)
+    B, K = 65, 3
+    x0 = np.random.default_rng(7).uniform([-0.5, -8.0, -5.0], [0.5, 8.0, 5.0], size=(B, 3))
+    try:
+        s.comm_init(0, 1, s.comm_unique_id())
+        s.loop_alloc(B, K, capi.LOG_ALL); s.loop_set_state(x0, x0); s.loop_set_schedule(p.schedules(K))
+        s.loop_run(0, K); s.loop_sync()
+        U, X = s.loop_get_log("U"), s.loop_get_log("X_HAT")
+        assert U.shape == (K, B, p.nu) and s.dev_ptr("U")[1] == 128
+        g = s.allgather_log("U", 0, 3)
+        assert g.shape == (1, 3, B, p.nu) and np.array_equal(g[0], U)
+        assert np.array_equal(s.allgather_log("X_HAT", 1, 1)[0], X[1:2])
+        assert np.array_equal(s.allgather_u()[0], U[-1])
+        assert np.array_equal(s.allgather_log("U", 0, 3)[0], U)
+        assert s.dev_ptr("coll_recv")[0] != 0
+        with pytest.raises(capi.MpcAmdError):
+            s.allgather_log("U", 1, 3)          # k0 + n > max_steps
+    finally:
+        s.close()
+
+
 def test_the_economic_librarys_own_communicator_gathers_its_device_log(pkg):
     """BASELINE configs[3] / [4] shard over eight GPUs: the per-model library carries the collective itself (enmpc_comm_*, enmpc_allgather_log: one
     ncclAllGather from the device log), no second library and no download in between; here with the one rank of the box, through shard.RcclComm - the

@@ -21,7 +21,7 @@ def build(p, extra_flags=(), verbose=False) -> str:
     extra_flags = tuple(extra_flags) + tuple(os.environ.get("EMU_EXTRA_FLAGS", "").split())      # (experiments: e.g. EMU_EXTRA_FLAGS=-DEC_SWEEP_SCAN python -m pytest tests/test_wave_emu.py)
     text = econcodegen.emit_econ_header(p)
     csrc = econcodegen.CSRC
-    srcs = [os.path.join(csrc, f) for f in ("mpc_enmpc.hip", "mpc_enmpc.hpp", "mpc_rk4s2.hpp", "mpc_sym.hpp", "mpc_comm.hpp")] + \
+    srcs = [os.path.join(csrc, f) for f in ("mpc_enmpc.hip", "mpc_enmpc.hpp", "mpc_rk4s2.hpp", "mpc_sym.hpp", "mpc_comm.hpp", "mpc_host.hpp")] + \
            [os.path.join(ROOT, "include", "mpc_enmpc.h"), os.path.join(HERE, "wave_emu.hpp"), os.path.join(HERE, "include", "hip", "hip_runtime.h")]
     hsh = hashlib.sha256((text + " ".join(FLAGS) + " ".join(extra_flags)).encode())
     for s in srcs:
