@@ -148,7 +148,7 @@ def closed_loop(p, nsteps, x0_p=None, x0_m=None, max_sqp=50, sqp_tol=1e-9):
     xs, us = xhat.copy(), u.copy()
     sched = p.schedules(nsteps)
     w = None
-    L = {k: [] for k in ("U", "X_HAT", "XS", "US", "Xp", "D_HAT", "STATUS_DYN", "STATUS_SS", "SQP_DYN", "ROW0", "W")}
+    L = {k: [] for k in ("U", "X_HAT", "XS", "US", "Xp", "D_HAT", "STATUS_DYN", "STATUS_SS", "SQP_DYN", "SQP_SS", "ROW0", "W")}
     for k in range(nsteps):
         t = k * p.h
         L["Xp"].append(x.copy()); L["X_HAT"].append(xhat.copy())
@@ -167,7 +167,7 @@ def closed_loop(p, nsteps, x0_p=None, x0_m=None, max_sqp=50, sqp_tol=1e-9):
         tg = no.target_solve(p, sched["usp"][k], sched["ysp"][k], dhat, xs, us, t=t, us_prev=us_prev)
         if tg["status"] != STATUS_INFEASIBLE:
             xs, us = tg["xs"], tg["us"]
-        L["XS"].append(xs.copy()); L["US"].append(us.copy()); L["STATUS_SS"].append(tg["status"])
+        L["XS"].append(xs.copy()); L["US"].append(us.copy()); L["STATUS_SS"].append(tg["status"]); L["SQP_SS"].append(tg["sqp_iters"])
         r = ocp_solve(p, xhat, xs, us, dhat, w, max_sqp=max_sqp, tol=sqp_tol, t=t, u_prev=u)
         L["W"].append(r["w"].copy())
         if r["status"] != STATUS_INFEASIBLE:
