@@ -1316,7 +1316,7 @@ __global__ __launch_bounds__(64, 1) void ocp_kernel_wv(const DevProblem *__restr
         X[j].put(X0);
     }
     for (int pass = 0;; pass++) {      // (terminal equality: wv_term_aim)
-        wv_solve<NS, NU, DU, NC, MASKED, NI>(P, T, q, iflag, X, S, P.max_iter);
+        wv_solve<NS, NU, DU, NC, MASKED, NI, ConstProblem, false, false, true>(P, T, q, iflag, X, S, P.max_iter);      // (RES_P: res[1] below)
         if (!P.term_cons || pass == 2 || !wv_term_aim<NS, NU, NC, NX, NI, Cfg>(N, q, iflag, aimv, itacc, X, S)) break;
     }
     MPC_UNROLL for (int j = 0; j < NI; j++) {

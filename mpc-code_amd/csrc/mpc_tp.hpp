@@ -66,12 +66,23 @@ struct TpCfg {
 // Horizon-wide sums and maxima = reductions over the 64 lanes of a wave, on the DPP network (no LDS round trips):
 // butterflies inside each row of 16 lanes (quad swaps, half-row mirror, row mirror), then row_bcast:15 / row_bcast:31
 // fold the four rows into lane 63, which is read back into scalar registers (the result is wave-uniform).
+// `old` is what a lane keeps when the control names no source lane for it or the row mask leaves its row out.  The quad permutes
+// (0x00 - 0xFF), row_half_mirror and row_mirror under the full row mask give every lane a source inside its own row of 16, so `old` is
+// never seen there: those go out with bound_ctrl on and the source as `old` - no destination tied to a second value, which costs a
+// v_mov_b32 pair per double otherwise.  (Every caller runs them with whole rows active: with bound_ctrl a switched-off source lane
+// would read as zero.)  The wave shifts and the row broadcasts under a partial row mask keep `old`: some lanes do see it.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_move(double old, double v)
 {
+    constexpr bool every_lane_has_a_source = ROW_MASK == 0xF && ((CTRL >= 0 && CTRL <= 0xFF) || CTRL == 0x140 || CTRL == 0x141);
     union { double d; int i[2]; } a, o, r; a.d = v; o.d = old;
-    r.i[0] = __builtin_amdgcn_update_dpp(o.i[0], a.i[0], CTRL, ROW_MASK, 0xF, false);
-    r.i[1] = __builtin_amdgcn_update_dpp(o.i[1], a.i[1], CTRL, ROW_MASK, 0xF, false);
+    if constexpr (every_lane_has_a_source) {
+        r.i[0] = __builtin_amdgcn_update_dpp(a.i[0], a.i[0], CTRL, 0xF, 0xF, true);
+        r.i[1] = __builtin_amdgcn_update_dpp(a.i[1], a.i[1], CTRL, 0xF, 0xF, true);
+    } else {
+        r.i[0] = __builtin_amdgcn_update_dpp(o.i[0], a.i[0], CTRL, ROW_MASK, 0xF, false);
+        r.i[1] = __builtin_amdgcn_update_dpp(o.i[1], a.i[1], CTRL, ROW_MASK, 0xF, false);
+    }
     return r.d;
 }
 // the neighbour lane's value over the whole wave: wave_shr:1 (lane i gets lane i - 1, lane 0 keeps `old`) and wave_shl:1 (lane i

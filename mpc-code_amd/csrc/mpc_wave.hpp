@@ -131,7 +131,8 @@ __device__ __forceinline__ double row16_max(double v)
 // those of instance 2 j + 1 - so X and S have NI / 2 entries, every "per instance" quantity of an entry is per lane (the same in the
 // lanes of a half: reductions run per half, branches on an instance's flags diverge by whole halves), and the caller reads verdicts
 // at a lane of the half.  The tile passes are the same; the sums are taken in the same tree order.
-template <int NS, int NU, bool HASM, int NC, bool MASKED, int NI, class PT, bool LTV = false, bool PAIR = false>
+// RES_P: S[j].res_p holds the primal residual of the last tested iterate on return (PAIR: always); otherwise it is left at zero.
+template <int NS, int NU, bool HASM, int NC, bool MASKED, int NI, class PT, bool LTV = false, bool PAIR = false, bool RES_P = false>
 __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q, const int *iflag,
                                          WvIterA<NS, NU, NC> (&X)[PAIR ? NI / 2 : NI], WvInst (&S)[PAIR ? NI / 2 : NI], int max_iter)
 {
@@ -218,8 +219,21 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         }
         MPC_UNROLL for (int i = 0; i < NS; i++) pi[i] = blk_on ? gz[i] : 0.0;
         Sj.mu_sum = rsum(blk_on ? mu_p : 0.0);
-        const double res_p = rmax(blk_on ? resp_p : 0.0), cres = rmax(blk_on ? cres_p : 0.0), lmax = rmax(blk_on ? lmax_p : 0.0);
-        const bool ok_cp = (cres <= 1.0) && (res_p <= kTolFeas);
+        // Feasibility, complementarity and the largest multiplier enter the verdict only through comparisons with a threshold.  dmax drops
+        // a NaN operand and the per-lane maxima start from 0.0, so no lane holds a NaN and the lanes beyond the horizon hold 0.0:
+        // "max <= t" is "no lane has x > t" and "max > t" is "some lane has x > t" - one vote over the wave each instead of a six-step
+        // reduction.  The value of res_p is reduced only for a caller that reports it (RES_P: the per-call kernel).
+        // PAIR keeps the reductions over its halves.
+        double resp_m = blk_on ? resp_p : 0.0, cres_m = blk_on ? cres_p : 0.0, lmax_m = blk_on ? lmax_p : 0.0;
+        // (opaque to the compiler, as they were as operands of the DPP moves: a comparison it can see through changes which products of
+        // this phase it fuses into their sums, i.e. the rounding of the iterate)
+        if constexpr (!PAIR) { resp_m = vreg(resp_m); cres_m = vreg(cres_m); lmax_m = vreg(lmax_m); }
+        double res_p = 0.0, cres = 0.0, lmax = 0.0;
+        bool ok_cp;
+        if constexpr (PAIR) {
+            res_p = rmax(resp_m); cres = rmax(cres_m); lmax = rmax(lmax_m);
+            ok_cp = (cres <= 1.0) && (res_p <= kTolFeas);
+        } else ok_cp = !__any((cres_m > 1.0 || resp_m > kTolFeas) ? 1 : 0);
         double rs_p = 0.0;
         if (LTV) {
             // pi_{k+1} = gz_{k+1} + A_{k+1}' pi_{k+2} (lane k holds block k = (u_k, z_{k+1}): its costate passes through the NEXT block's A):
@@ -257,12 +271,17 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         }
         double res_s = Sj.res_s;
         if (it == 0 || ok_cp) res_s = rmax(blk_on ? rs_p : 0.0);
-        Sj.mu = Sj.mu_sum * Sj.inv_ncon; Sj.res_s = res_s; Sj.res_p = res_p;
+        Sj.mu = Sj.mu_sum * Sj.inv_ncon; Sj.res_s = res_s;
+        if constexpr (PAIR) Sj.res_p = res_p;
+        else if constexpr (RES_P) Sj.res_p = wave_max(resp_m);
         if (it == 0) Sj.gscale = dmax(1.0, P.term_cons ? dmin(res_s, P.term_gcap) : res_s);      // mpc_device.hpp:rpdip_lane
         Sj.stall = ok_cp ? Sj.stall + 1 : 0;
+        bool lm_big;
+        if constexpr (PAIR) lm_big = lmax > kInfeasZ * Sj.gscale;
+        else lm_big = __any(lmax_m > kInfeasZ * Sj.gscale ? 1 : 0) != 0;
         int verdict = -1;
         if (ok_cp && (res_s <= kTolStat * Sj.gscale + P.term_floor || (Sj.stall > kStallMax && res_s <= kTolStatAcc * Sj.gscale + P.term_floor))) verdict = kSolved;
-        else if (lmax > kInfeasZ * Sj.gscale || !(fabs(Sj.mu) < 1.0e300)) verdict = kInfeasible;
+        else if (lm_big || !(fabs(Sj.mu) < 1.0e300)) verdict = kInfeasible;
         else if (it == max_iter) verdict = kMaxIter;
         if (verdict >= 0) { Sj.on = false; Sj.status = verdict; Sj.iters = it; }
     };
