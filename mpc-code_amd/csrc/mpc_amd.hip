@@ -6,15 +6,10 @@
 // fails loudly when the device path is unavailable.
 #include "../../include/mpc_amd.h"
 #include "mpc_device.hpp"
+#include "mpc_lane_step.hpp"      // (OcpArgs, LoopArgs, plant_next; the phases of the instance-per-lane step)
 #include "mpc_tp.hpp"
 #include "mpc_wave.hpp"
 #include "mpc_soft.hpp"
-#ifdef MPC_NL_PLANT_HEADER
-// A non-linear plant for the fused closed loop (Ex_LMPC_nlplant.py, Ex_LMPCxp_nlplant.py: linear controller, User_fxp_Cont as the
-// simulated process): struct NlPlant { NXP, NU, MX; __device__ static void f(x, u, t, xdot); } generated from the traced Ex-file
-// function (mpc-code_amd/nlcodegen.py:emit_plant_header); a library built with it carries exactly one dimension set.
-#include MPC_NL_PLANT_HEADER
-#endif
 
 #include <hip/hip_runtime.h>
 #include "mpc_comm.hpp"      // (with mpc_host.hpp: error state, DevBuf, the SoA staging, the log table)
@@ -65,14 +60,6 @@ extern "C" const char *mpc_last_error(void) { return g_err; }
 // ---------------------------------------------------------------------------------------------------
 // kernels.  Device arrays are structure-of-arrays [dim][Bs], instance index fastest.
 // ---------------------------------------------------------------------------------------------------
-struct OcpArgs {
-    const double *xhat, *xs, *us, *dhat, *u_prev;   // in
-    double *u_out, *xnext_out, *res;                // out ([nu][Bs], [nx][Bs], [3][Bs])
-    int32_t *status, *iters;
-    double *ws;                                     // workspace rows
-    int B; size_t Bs;
-};
-
 template <int NX, int NU, int NY, int ND, bool DU, int NG, int NC, bool MASKED>
 __global__ __launch_bounds__(64) void ocp_kernel(const DevProblem *__restrict__ Pp, OcpArgs a)
 {
@@ -81,18 +68,14 @@ __global__ __launch_bounds__(64) void ocp_kernel(const DevProblem *__restrict__ 
     if (b >= a.B) return;
     const DevProblem &P = *Pp;
     double xhat[NX], xs[NX], us[NU], up[NU], dh[ND > 0 ? ND : 1];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { xhat[i] = a.xhat[i * a.Bs + b]; xs[i] = a.xs[i * a.Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < NU; i++) { us[i] = a.us[i * a.Bs + b]; up[i] = a.u_prev[i * a.Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = a.dhat[i * a.Bs + b];
+    ocp_load<ND>(a, b, xhat, xs, us, up, dh);
     OcpInst<NS, NU> q;
     build_inst<NX, NU, NY, ND, DU, NG>(P, xhat, xs, us, dh, up, q);
     StageConst<NS, NU> C;
     load_stage_const<NS, NU, DU>(P, C);
-    constexpr int SL = BlkLayout<NS, NU, NC>::SLOTS;
-    Ws ws{(gv2d *)((v2d *)a.ws + ((size_t)blockIdx.x * (P.N + 2) + 1) * SL * 64), P.N, SL, (int)threadIdx.x};
+    const Ws ws = lane_ws<NS, NU, NC>(a.ws, P.N);
     double u0[NU], z1[NS], res[3];
-    int it;
-    int st, it_sum = 0;
+    int it, st, it_sum = 0;
     for (int pass = 0;; pass++) {      // (terminal equality: up to two more passes with the terminal reference aimed off, mpc_device.hpp:term_aim)
         st = rpdip_lane<NS, NU, DU, NC, MASKED>(P, C, q, ws, P.max_iter, false, 0.0, u0, z1, res, it);
         it_sum += it;
@@ -100,12 +83,7 @@ __global__ __launch_bounds__(64) void ocp_kernel(const DevProblem *__restrict__ 
     }
     it = it_sum;
     if (P.term_cons && st != kInfeasible && term_missed<NS, NU, NC, NX>(P, ws, q)) st = kInfeasible;
-    a.status[b] = st; a.iters[b] = it;
-    MPC_UNROLL for (int i = 0; i < 3; i++) a.res[i * a.Bs + b] = res[i];
-    if (st != kInfeasible) {
-        MPC_UNROLL for (int i = 0; i < NU; i++) a.u_out[i * a.Bs + b] = (DU && P.in_is_du) ? z1[DU ? NX + i : 0] : u0[i];      // input v = u - u_prev: u is the u_prev part of z_1
-        MPC_UNROLL for (int i = 0; i < NX; i++) a.xnext_out[i * a.Bs + b] = z1[i];
-    }
+    ocp_store<NX, DU>(P, a, b, st, it, res, u0, z1);
 }
 
 // the soft problem of one instance: stage data of the hard problem (build_inst with y_bounded = 0: the stage boxes are the state bounds alone) + the output rows and their weight
@@ -142,9 +120,7 @@ __global__ __launch_bounds__(64) void ocp_kernel_soft(const DevProblem *__restri
     if (b >= a.B) return;
     const DevProblem &P = *Pp;
     double xhat[NX], xs[NX], us[NU], up[NU], dh[ND > 0 ? ND : 1];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { xhat[i] = a.xhat[i * a.Bs + b]; xs[i] = a.xs[i * a.Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < NU; i++) { us[i] = a.us[i * a.Bs + b]; up[i] = a.u_prev[i * a.Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = a.dhat[i * a.Bs + b];
+    ocp_load<ND>(a, b, xhat, xs, us, up, dh);
     OcpInst<NS, NU> q;
     build_inst<NX, NU, NY, ND, DU, NG>(P, xhat, xs, us, dh, up, q);      // (y_bounded = 0 in a soft problem: the stage boxes are the state bounds alone)
     SoftProb<NS, NU, NY> S;
@@ -154,13 +130,8 @@ __global__ __launch_bounds__(64) void ocp_kernel_soft(const DevProblem *__restri
     double u0[NU], z1[NS], sl[2 * NY], res[3];
     int it;
     const int st = soft_solve<NS, NU, NY, 64>(S, ws, u0, z1, sl, res, it);
-    a.status[b] = st; a.iters[b] = it;
-    MPC_UNROLL for (int i = 0; i < 3; i++) a.res[i * a.Bs + b] = res[i];
     for (int i = 0; i < 2 * NY; i++) w.sl_out[i * a.Bs + b] = sl[i];
-    if (st != kInfeasible) {
-        MPC_UNROLL for (int i = 0; i < NU; i++) a.u_out[i * a.Bs + b] = (DU && P.in_is_du) ? z1[DU ? NX + i : 0] : u0[i];
-        MPC_UNROLL for (int i = 0; i < NX; i++) a.xnext_out[i * a.Bs + b] = z1[i];
-    }
+    ocp_store<NX, DU>(P, a, b, st, it, res, u0, z1);
 }
 
 // The same call with time-varying model parameters over the horizon (def_px / def_py, MPC_code.py:492-497, Control_Calc.py:43-57):
@@ -172,66 +143,22 @@ struct OcpPxyArgs { OcpArgs o; const double *px, *py; double *lin; };      // px
 template <int NX, int NU, int NY, int ND, bool DU, int NG>
 __global__ __launch_bounds__(64) void ocp_kernel_pxy(const DevProblem *__restrict__ Pp, OcpPxyArgs w)
 {
-    constexpr int NS = NX + (DU ? NU : 0) + NG, NB = NX + (DU ? NU : 0), NC = NS + NU, NLTV = NS * (NS + NU + 1), NLIN = NLTV + 2 * NS;
+    constexpr int NS = NX + (DU ? NU : 0) + NG, NC = NS + NU, NLTV = NS * (NS + NU + 1), NLIN = NLTV + 2 * NS;
     const OcpArgs &a = w.o;
     const int lane = threadIdx.x, b = blockIdx.x * 64 + lane;
     if (b >= a.B) return;
     const DevProblem &P = *Pp;
-    const int N = P.N;
     double xhat[NX], xs[NX], us[NU], up[NU], dh[ND > 0 ? ND : 1];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { xhat[i] = a.xhat[i * a.Bs + b]; xs[i] = a.xs[i * a.Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < NU; i++) { us[i] = a.us[i * a.Bs + b]; up[i] = a.u_prev[i * a.Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = a.dhat[i * a.Bs + b];
+    ocp_load<ND>(a, b, xhat, xs, us, up, dh);
     OcpInst<NS, NU> q;
     build_inst<NX, NU, NY, ND, DU, NG>(P, xhat, xs, us, dh, up, q);
     StageConst<NS, NU> C;
     load_stage_const<NS, NU, DU>(P, C);
-    double e0[NY];      // output offsets without py
-    MPC_UNROLL for (int i = 0; i < NY; i++) { double e = P.fyc[i]; MPC_UNROLL for (int j = 0; j < ND; j++) e += P.Cd[i][j] * dh[j]; e0[i] = e; }
-    if (P.y_bounded && w.py) {      // the stage-0 row is a test of the given x_0 (Control_Calc.py:128-151), with py_0
-        q.ok0 = true;
-        MPC_UNROLL for (int i = 0; i < NY; i++) {
-            double y0 = e0[i] + w.py[(size_t)i * a.Bs + b];
-            MPC_UNROLL for (int j = 0; j < NX; j++) y0 += P.Cm[i][j] * xhat[j];
-            const double rl = kBoundRelax * dmax(1.0, fabs(P.ymin[i])), rh = kBoundRelax * dmax(1.0, fabs(P.ymax[i]));
-            if (!(y0 >= P.ymin[i] - rl) || !(y0 <= P.ymax[i] + rh)) q.ok0 = false;
-        }
-    }
-    double *const lin = w.lin + (size_t)blockIdx.x * N * NLIN * 64 + lane;
-    for (int k = 0; k < N; k++) {
-        double *lb = lin + (size_t)k * NLIN * 64;
-        double pxk[NX];
-        MPC_UNROLL for (int i = 0; i < NX; i++) pxk[i] = w.px ? w.px[((size_t)k * NX + i) * a.Bs + b] : 0.0;
-        MPC_UNROLL for (int i = 0; i < NS; i++) {
-            MPC_UNROLL for (int j = 0; j < NS; j++) lb[(i * NS + j) * 64] = C.A[i][j];
-            MPC_UNROLL for (int j = 0; j < NU; j++) lb[(NS * NS + i * NU + j) * 64] = C.B[i][j];
-            double c = q.c[i];
-            if (i < NX) c += pxk[i < NX ? i : 0];
-            if (i >= NB) { const int r = P.yg_row[i >= NB ? i - NB : 0]; MPC_UNROLL for (int j = 0; j < NX; j++) c += P.Cm[r][j] * pxk[j]; }      // w+ = C_i x+
-            lb[(NS * NS + NS * NU + i) * 64] = c;
-        }
-        // bounds of z_{k+1}: the constant boxes, cut by the output rows of stage k + 1 (none at the terminal state)
-        double lo[NS], hi[NS];
-        const bool end = k == N - 1;
-        MPC_UNROLL for (int i = 0; i < NS; i++) { lo[i] = end ? P.zlo_e[i] : P.zlo_m[i]; hi[i] = end ? P.zhi_e[i] : P.zhi_m[i]; }
-        if (P.y_bounded && !end) {
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                const double e = e0[i] + (w.py ? w.py[((size_t)(k + 1) * NY + i) * a.Bs + b] : 0.0);
-                const double sc = P.ymap_scale[i];
-                const double aa = (P.ymin[i] - e) / sc, bb = (P.ymax[i] - e) / sc;
-                const double l = sc > 0 ? aa : bb, h = sc > 0 ? bb : aa;
-                const int idx = P.ymap_idx[i];
-                MPC_UNROLL for (int j = 0; j < NS; j++)
-                    if (j == idx) { lo[j] = dmax(lo[j], l); hi[j] = dmin(hi[j], h); }
-            }
-        }
-        MPC_UNROLL for (int i = 0; i < NS; i++) { lb[(NLTV + i) * 64] = lo[i]; lb[(NLTV + NS + i) * 64] = hi[i]; }
-    }
-    constexpr int SL = BlkLayout<NS, NU, NC>::SLOTS;
-    Ws ws{(gv2d *)((v2d *)a.ws + ((size_t)blockIdx.x * (N + 2) + 1) * SL * 64), N, SL, lane};
+    double *const lin = w.lin + (size_t)blockIdx.x * P.N * NLIN * 64 + lane;
+    lane_pxy_slab<NX, NY, ND, DU, NG>(P, C, q, xhat, dh, w.px ? w.px + b : nullptr, w.py ? w.py + b : nullptr, a.Bs, lin);
+    const Ws ws = lane_ws<NS, NU, NC>(a.ws, P.N);
     double u0[NU], z1[NS], res[3];
-    int it;
-    int st, it_sum = 0;
+    int it, st, it_sum = 0;
     for (int pass = 0;; pass++) {
         st = rpdip_lane<NS, NU, DU, NC, true, true>(P, C, q, ws, P.max_iter, false, 0.0, u0, z1, res, it, lin, 1, NLIN, NLTV);
         it_sum += it;
@@ -239,12 +166,7 @@ __global__ __launch_bounds__(64) void ocp_kernel_pxy(const DevProblem *__restric
     }
     it = it_sum;
     if (P.term_cons && st != kInfeasible && term_missed<NS, NU, NC, NX>(P, ws, q)) st = kInfeasible;
-    a.status[b] = st; a.iters[b] = it;
-    MPC_UNROLL for (int i = 0; i < 3; i++) a.res[i * a.Bs + b] = res[i];
-    if (st != kInfeasible) {
-        MPC_UNROLL for (int i = 0; i < NU; i++) a.u_out[i * a.Bs + b] = (DU && P.in_is_du) ? z1[DU ? NX + i : 0] : u0[i];
-        MPC_UNROLL for (int i = 0; i < NX; i++) a.xnext_out[i * a.Bs + b] = z1[i];
-    }
+    ocp_store<NX, DU>(P, a, b, st, it, res, u0, z1);
 }
 
 struct TargetArgs {
@@ -294,90 +216,23 @@ __global__ __launch_bounds__(64) void kf_kernel(const DevProblem *__restrict__ P
         MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
         innov[i] = a.y[i * a.Bs + b] - yh;
     }
-    if (P.estimator == MPC_EST_KALMAN) {
-        double Pk[NE][NE];
-        MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) Pk[i][j] = a.Pk[(i * NE + j) * a.Bs + b]; }
-        kalman_lane<NE, NY>(P, xi, Pk, innov);
-        MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) a.Pk[(i * NE + j) * a.Bs + b] = Pk[i][j]; }
-    } else if (P.estimator == MPC_EST_FIXED_GAIN) {
-        MPC_UNROLL for (int i = 0; i < NE; i++) { double s = 0.0; MPC_UNROLL for (int l = 0; l < NY; l++) s += P.Kfix[i][l] * innov[l]; xi[i] += s; }
-    }
+    lane_correct<NE, NY>(P, a.Pk, a.Bs, b, xi, innov);
     MPC_UNROLL for (int i = 0; i < NE; i++) a.xi[i * a.Bs + b] = xi[i];
 }
 
-// The closed loop, MPC_code.py:485-827: `nsteps` consecutive steps per launch, state read from / written
-// back to HBM once per launch.
-struct LoopArgs {
-    double *x, *xhat, *dhat, *Pk, *u, *xs, *us;      // state [dim][Bs]
-    const double *ysp, *usp, *pxp, *pyp;             // schedules [step][dim], already offset to k0
-    double *U, *XHAT, *XS, *US, *YS, *XP, *DHAT;     // logs [step][dim][Bs] offset to k0, or nullptr
-    int32_t *st_dyn, *st_ss, *it_dyn, *it_ss;        // logs [step][Bs] offset to k0, or nullptr
-    int32_t *ws_valid;                               // [Bs] 1 if the workspace holds a solved OCP of the previous step
-    int32_t *kf_valid;                               // [Bs] 1 if Kg / Pn hold the filter gain of this step and the prior after it
-    double *Kg, *Pn;                                 // [ne*ny][Bs], [ne*ne][Bs] (horizon-parallel kernel: computed one step ahead)
-    double *tw; int32_t *tw_valid;                   // warm start of the target solve: [2*(nu-nh_ss) + 3*(nx+nu+ny+ng_ss)][Bs], [Bs]
-    double *ws;
-    int B, nsteps; size_t Bs;
-    int N;                                           // horizon (host side: sizes the dynamic LDS of the wave-autonomous kernel)
-    double t0, h;                                    // time of the launch's first step, sampling interval (a user plant integrates in time)
-    int wv_ni;                                       // wave-autonomous kernel: instances per wave (0 = by batch size; option "wave_instances")
-    const double *px_h, *py_h;                       // def_px / def_py over the horizon, [step][N][nx] / [step][N][ny] offset to k0 (loop_kernel_pxy), or nullptr
-    double *lin;                                     // loop_kernel_pxy: slab of per-block stage data
-    double *SL, *soft_ws, *sl_keep;                  // loop_kernel_soft: log of the slacks [step][2 ny][Bs] offset to k0 (or nullptr), the arrowhead solver's workspace, the last accepted slacks [2 ny][Bs]
-};
-
-// x_p(t + h) (MPC_code.py:813-816).  Linear plant: Ap x + Bp u + pxp (Utilities.py:45-49).  User plant: MX classical RK4 steps of
-// dx/dt = f(x, u, t) over h with the inputs held and time carried along, then + pxp (Utilities.py:58-82, casadi.simpleRK; LinPar).
-template <int NXP, int NU, class PT>
-__device__ __forceinline__ void plant_next(const PT &P, const double (&x)[NXP], const double (&u)[NU], const double *pxp_k, double t, double h, double (&xn)[NXP])
-{
-#ifdef MPC_NL_PLANT_HEADER
-    static_assert(NlPlant::NXP == NXP && NlPlant::NU == NU, "the plant header belongs to another dimension set");
-    (void)P;
-    const double dt = h / NlPlant::MX;
-    double xx[NXP];
-    MPC_UNROLL for (int i = 0; i < NXP; i++) xx[i] = x[i];
-    for (int s = 0; s < NlPlant::MX; s++) {
-        const double ts = t + s * dt;
-        double k1[NXP], k2[NXP], k3[NXP], k4[NXP], xa[NXP];
-        NlPlant::f(xx, u, ts, k1);
-        MPC_UNROLL for (int i = 0; i < NXP; i++) xa[i] = xx[i] + 0.5 * dt * k1[i];
-        NlPlant::f(xa, u, ts + 0.5 * dt, k2);
-        MPC_UNROLL for (int i = 0; i < NXP; i++) xa[i] = xx[i] + 0.5 * dt * k2[i];
-        NlPlant::f(xa, u, ts + 0.5 * dt, k3);
-        MPC_UNROLL for (int i = 0; i < NXP; i++) xa[i] = xx[i] + dt * k3[i];
-        NlPlant::f(xa, u, ts + dt, k4);
-        MPC_UNROLL for (int i = 0; i < NXP; i++) xx[i] += dt / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
-    }
-    MPC_UNROLL for (int i = 0; i < NXP; i++) xn[i] = xx[i] + pxp_k[i];
-#else
-    (void)t; (void)h;
-    MPC_UNROLL for (int i = 0; i < NXP; i++) {
-        double v = pxp_k[i];
-        MPC_UNROLL for (int j = 0; j < NXP; j++) v += P.Ap[i][j] * x[j];
-        MPC_UNROLL for (int j = 0; j < NU; j++) v += P.Bp[i][j] * u[j];
-        xn[i] = v;
-    }
-#endif
-}
-
+// The closed loop (LoopArgs), one instance per lane: the phases of mpc_lane_step.hpp around the hard OCP with its warm start.
 template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64) void loop_kernel(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
-    constexpr int NS = NX + (DU ? NU : 0) + NG, NE = NX + ND;
+    constexpr int NS = NX + (DU ? NU : 0) + NG;
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     const DevProblem &P = *Pp;
-    const size_t Bs = a.Bs;
     double x[NXP], xh[NX], dh[ND > 0 ? ND : 1], u[NU], xs[NX], us[NU];
-    MPC_UNROLL for (int i = 0; i < NXP; i++) x[i] = a.x[i * Bs + b];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { xh[i] = a.xhat[i * Bs + b]; xs[i] = a.xs[i * Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = a.dhat[i * Bs + b];
-    MPC_UNROLL for (int i = 0; i < NU; i++) { u[i] = a.u[i * Bs + b]; us[i] = a.us[i * Bs + b]; }
+    lane_state_load<ND>(a, b, x, xh, dh, u, xs, us);
     StageConst<NS, NU> C;
     load_stage_const<NS, NU, DU>(P, C);
-    constexpr int SL = BlkLayout<NS, NU, NC>::SLOTS;
-    Ws ws{(gv2d *)((v2d *)a.ws + ((size_t)blockIdx.x * (P.N + 2) + 1) * SL * 64), P.N, SL, (int)threadIdx.x};
+    const Ws ws = lane_ws<NS, NU, NC>(a.ws, P.N);
     bool ws_valid = a.ws_valid[b] != 0;
     for (int k = 0; k < a.nsteps; k++) {
         // data of the previous step, for the warm-start test: prediction of xhat, dhat, target
@@ -385,56 +240,16 @@ __global__ __launch_bounds__(64) void loop_kernel(const DevProblem *__restrict__
         MPC_UNROLL for (int i = 0; i < NX; i++) { xh_pred[i] = xh[i]; xs_prev[i] = xs[i]; }
         MPC_UNROLL for (int i = 0; i < ND; i++) dh_prev[i] = dh[i];
         MPC_UNROLL for (int i = 0; i < NU; i++) us_prev[i] = us[i];
-        if (a.XP) { MPC_UNROLL for (int i = 0; i < NXP; i++) a.XP[((size_t)k * NXP + i) * Bs + b] = x[i]; }
-        if (a.XHAT) { MPC_UNROLL for (int i = 0; i < NX; i++) a.XHAT[((size_t)k * NX + i) * Bs + b] = xh[i]; }
-        // ---- measure and estimate (MPC_code.py:524-534, 577-668) ---------------------------------
-        if (P.estimator != MPC_EST_NONE) {
-            double xi[NE], innov[NY];
-            MPC_UNROLL for (int i = 0; i < NX; i++) xi[i] = xh[i];
-            MPC_UNROLL for (int i = 0; i < ND; i++) xi[NX + i] = dh[i];
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                double yh = P.fyc[i], yy = a.pyp[k * NY + i];
-                MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
-                MPC_UNROLL for (int j = 0; j < NXP; j++) yy += P.Cp[i][j] * x[j];
-                innov[i] = yy - yh;
-            }
-            if (P.estimator == MPC_EST_KALMAN) {
-                double Pk[NE][NE];
-                MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) Pk[i][j] = a.Pk[(i * NE + j) * Bs + b]; }
-                kalman_lane<NE, NY>(P, xi, Pk, innov);
-                MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) a.Pk[(i * NE + j) * Bs + b] = Pk[i][j]; }
-            } else {
-                MPC_UNROLL for (int i = 0; i < NE; i++) { double s = 0.0; MPC_UNROLL for (int l = 0; l < NY; l++) s += P.Kfix[i][l] * innov[l]; xi[i] += s; }
-            }
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = xi[i];
-            MPC_UNROLL for (int i = 0; i < ND; i++) { double d = xi[NX + i]; if (P.has_dsat) d = dmin(dmax(d, P.dmin[i]), P.dmax[i]); dh[i] = d; }
-        }
-        if (a.DHAT) { MPC_UNROLL for (int i = 0; i < ND; i++) a.DHAT[((size_t)k * ND + i) * Bs + b] = dh[i]; }
-        // ---- target (MPC_code.py:693-718): keep the previous one when infeasible ------------------
-        double usp[NU], ysp[NY], xs_n[NX], us_n[NU], ys_n[NY];
-        MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
-        MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
-        int it_ss;
-        const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, a.tw + b, Bs, a.tw_valid + b);
-        if (st_ss != kInfeasible) {
-            MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
-            MPC_UNROLL for (int i = 0; i < NU; i++) us[i] = us_n[i];
-        }
-        if (a.XS) { MPC_UNROLL for (int i = 0; i < NX; i++) a.XS[((size_t)k * NX + i) * Bs + b] = xs[i]; }
-        if (a.US) { MPC_UNROLL for (int i = 0; i < NU; i++) a.US[((size_t)k * NU + i) * Bs + b] = us[i]; }
-        if (a.YS) {   // ys = Fy_model(xs, us, dhat), MPC_code.py:730
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                double v = P.fyc[i];
-                MPC_UNROLL for (int j = 0; j < NX; j++) v += P.Cm[i][j] * xs[j];
-                MPC_UNROLL for (int j = 0; j < ND; j++) v += P.Cd[i][j] * dh[j];
-                a.YS[((size_t)k * NY + i) * Bs + b] = v;
-            }
-        }
-        // ---- OCP (MPC_code.py:733-805) -------------------------------------------------------------
+        lane_log<NXP>(a.XP, k, a.Bs, b, x);
+        lane_log<NX>(a.XHAT, k, a.Bs, b, xh);
+        lane_estimate<NY, ND>(P, a, k, b, x, xh, dh);
+        lane_log<ND>(a.DHAT, k, a.Bs, b, dh);
+        int it_ss, it_dyn;
+        const int st_ss = lane_target<NY, ND, NGS, NHS>(P, a, k, b, dh, xs, us, it_ss, true);
+        lane_log_ys<NY, ND>(P, a, k, b, xs, dh);
         OcpInst<NS, NU> q;
         build_inst<NX, NU, NY, ND, DU, NG>(P, xh, xs, us, dh, u, q);
         double u0[NU], z1[NS], res[3];
-        int it_dyn;
         double delta = 0.0;
         MPC_UNROLL for (int i = 0; i < NX; i++) delta = dmax(delta, dmax(fabs(xh[i] - xh_pred[i]), fabs(xs[i] - xs_prev[i])));
         MPC_UNROLL for (int i = 0; i < ND; i++) delta = dmax(delta, fabs(dh[i] - dh_prev[i]));
@@ -449,139 +264,51 @@ __global__ __launch_bounds__(64) void loop_kernel(const DevProblem *__restrict__
         it_dyn = it_sum;
         if (P.term_cons && st_dyn != kInfeasible && term_missed<NS, NU, NC, NX>(P, ws, q)) st_dyn = kInfeasible;
         ws_valid = st_dyn == kSolved;
-        if (st_dyn != kInfeasible) {
-            MPC_UNROLL for (int i = 0; i < NU; i++) u[i] = (DU && P.in_is_du) ? z1[DU ? NX + i : 0] : u0[i];          // :798
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = z1[i];         // :799
-        } else {                                                           // :804-805 hold u, propagate the model
-            double xn[NX];
-            MPC_UNROLL for (int i = 0; i < NX; i++) {
-                double v = P.fxc[i];
-                MPC_UNROLL for (int j = 0; j < NX; j++) v += P.Am[i][j] * xh[j];
-                MPC_UNROLL for (int j = 0; j < NU; j++) v += P.Bm[i][j] * u[j];
-                MPC_UNROLL for (int j = 0; j < ND; j++) v += P.Bd[i][j] * dh[j];
-                xn[i] = v;
-            }
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = xn[i];
-        }
-        if (a.U) { MPC_UNROLL for (int i = 0; i < NU; i++) a.U[((size_t)k * NU + i) * Bs + b] = u[i]; }
-        if (a.st_dyn) { a.st_dyn[(size_t)k * Bs + b] = st_dyn; a.st_ss[(size_t)k * Bs + b] = st_ss; a.it_dyn[(size_t)k * Bs + b] = it_dyn; a.it_ss[(size_t)k * Bs + b] = it_ss; }
-        // ---- plant (MPC_code.py:813-816) -----------------------------------------------------------
-        {
-            double xn[NXP];
-            plant_next<NXP, NU>(P, x, u, a.pxp + k * NXP, a.t0 + k * a.h, a.h, xn);
-            MPC_UNROLL for (int i = 0; i < NXP; i++) x[i] = xn[i];
-        }
+        lane_accept_or_hold<ND, DU>(P, a, k, b, st_dyn, st_ss, it_dyn, it_ss, u0, z1, u, xh, dh);
+        lane_plant_step(P, a, k, x, u, a.pxp + k * NXP);
     }
-    MPC_UNROLL for (int i = 0; i < NXP; i++) a.x[i * Bs + b] = x[i];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { a.xhat[i * Bs + b] = xh[i]; a.xs[i * Bs + b] = xs[i]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) a.dhat[i * Bs + b] = dh[i];
-    MPC_UNROLL for (int i = 0; i < NU; i++) { a.u[i * Bs + b] = u[i]; a.us[i * Bs + b] = us[i]; }
+    lane_state_store<ND>(a, b, x, xh, dh, u, xs, us);
     a.ws_valid[b] = ws_valid ? 1 : 0;
 }
 
-// The closed loop of a problem with SOFT output constraints (slacks = True; mpc_soft.hpp): loop_kernel's step - instance per lane, the same estimator, target and
-// plant code - with the arrowhead solver as its OCP, cold every step like ocp_kernel_soft: a fused run is the loop of the three C-ABI calls per step.  The optimal
-// slacks of every step go to the log SL (MPC_code.py:800).  One instantiation per dimension set.
+// The closed loop of a problem with SOFT output constraints (slacks = True; mpc_soft.hpp): loop_kernel's step - the same phase functions for estimator, target,
+// hold rule and plant - with the arrowhead solver as its OCP, cold every step like ocp_kernel_soft: a fused run is the loop of the three C-ABI calls per step.
+// The optimal slacks of every step go to the log SL (MPC_code.py:800).  One instantiation per dimension set.
 template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64) void loop_kernel_soft(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
-    constexpr int NS = NX + (DU ? NU : 0) + NG, NE = NX + ND;
+    constexpr int NS = NX + (DU ? NU : 0) + NG;
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= a.B) return;
     const DevProblem &P = *Pp;
     const size_t Bs = a.Bs;
     double x[NXP], xh[NX], dh[ND > 0 ? ND : 1], u[NU], xs[NX], us[NU];
-    MPC_UNROLL for (int i = 0; i < NXP; i++) x[i] = a.x[i * Bs + b];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { xh[i] = a.xhat[i * Bs + b]; xs[i] = a.xs[i * Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = a.dhat[i * Bs + b];
-    MPC_UNROLL for (int i = 0; i < NU; i++) { u[i] = a.u[i * Bs + b]; us[i] = a.us[i * Bs + b]; }
+    lane_state_load<ND>(a, b, x, xh, dh, u, xs, us);
     using LY = SoftLayout<NS, NU, NY>;
     double *const ws = a.soft_ws + (size_t)blockIdx.x * LY::FIELDS * P.N * 64 + threadIdx.x;
     double slk[2 * NY];      // the slacks of the last accepted OCP (MPC_code.py:800, 808-809: Sl.append(sl_k))
     for (int i = 0; i < 2 * NY; i++) slk[i] = a.sl_keep[i * Bs + b];
     for (int k = 0; k < a.nsteps; k++) {
-        if (a.XP) { MPC_UNROLL for (int i = 0; i < NXP; i++) a.XP[((size_t)k * NXP + i) * Bs + b] = x[i]; }
-        if (a.XHAT) { MPC_UNROLL for (int i = 0; i < NX; i++) a.XHAT[((size_t)k * NX + i) * Bs + b] = xh[i]; }
-        // ---- measure and estimate (MPC_code.py:524-534, 577-668) ---------------------------------
-        if (P.estimator != MPC_EST_NONE) {
-            double xi[NE], innov[NY];
-            MPC_UNROLL for (int i = 0; i < NX; i++) xi[i] = xh[i];
-            MPC_UNROLL for (int i = 0; i < ND; i++) xi[NX + i] = dh[i];
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                double yh = P.fyc[i], yy = a.pyp[k * NY + i];
-                MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
-                MPC_UNROLL for (int j = 0; j < NXP; j++) yy += P.Cp[i][j] * x[j];
-                innov[i] = yy - yh;
-            }
-            if (P.estimator == MPC_EST_KALMAN) {
-                double Pk[NE][NE];
-                MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) Pk[i][j] = a.Pk[(i * NE + j) * Bs + b]; }
-                kalman_lane<NE, NY>(P, xi, Pk, innov);
-                MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) a.Pk[(i * NE + j) * Bs + b] = Pk[i][j]; }
-            } else {
-                MPC_UNROLL for (int i = 0; i < NE; i++) { double s_ = 0.0; MPC_UNROLL for (int l = 0; l < NY; l++) s_ += P.Kfix[i][l] * innov[l]; xi[i] += s_; }
-            }
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = xi[i];
-            MPC_UNROLL for (int i = 0; i < ND; i++) { double d = xi[NX + i]; if (P.has_dsat) d = dmin(dmax(d, P.dmin[i]), P.dmax[i]); dh[i] = d; }
-        }
-        if (a.DHAT) { MPC_UNROLL for (int i = 0; i < ND; i++) a.DHAT[((size_t)k * ND + i) * Bs + b] = dh[i]; }
-        // ---- target (MPC_code.py:693-718): keep the previous one when infeasible ------------------
-        double usp[NU], ysp[NY], xs_n[NX], us_n[NU], ys_n[NY];
-        MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
-        MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
-        int it_ss;
-        const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, a.tw + b, Bs, a.tw_valid + b);
-        if (st_ss != kInfeasible) {
-            MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
-            MPC_UNROLL for (int i = 0; i < NU; i++) us[i] = us_n[i];
-        }
-        if (a.XS) { MPC_UNROLL for (int i = 0; i < NX; i++) a.XS[((size_t)k * NX + i) * Bs + b] = xs[i]; }
-        if (a.US) { MPC_UNROLL for (int i = 0; i < NU; i++) a.US[((size_t)k * NU + i) * Bs + b] = us[i]; }
-        if (a.YS) {   // ys = Fy_model(xs, us, dhat), MPC_code.py:730
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                double v = P.fyc[i];
-                MPC_UNROLL for (int j = 0; j < NX; j++) v += P.Cm[i][j] * xs[j];
-                MPC_UNROLL for (int j = 0; j < ND; j++) v += P.Cd[i][j] * dh[j];
-                a.YS[((size_t)k * NY + i) * Bs + b] = v;
-            }
-        }
+        lane_log<NXP>(a.XP, k, Bs, b, x);
+        lane_log<NX>(a.XHAT, k, Bs, b, xh);
+        lane_estimate<NY, ND>(P, a, k, b, x, xh, dh);
+        lane_log<ND>(a.DHAT, k, Bs, b, dh);
+        int it_ss, it_dyn;
+        const int st_ss = lane_target<NY, ND, NGS, NHS>(P, a, k, b, dh, xs, us, it_ss, true);
+        lane_log_ys<NY, ND>(P, a, k, b, xs, dh);
         // ---- OCP with the shared slack vector (MPC_code.py:733-805; Control_Calc.py:39-40,186-188,228-239) ---------------------------------------------
         OcpInst<NS, NU> q;
         build_inst<NX, NU, NY, ND, DU, NG>(P, xh, xs, us, dh, u, q);
         SoftProb<NS, NU, NY> S;
         soft_prob_fill<NX, NU, NY, ND, DU, NS>(P, q, dh, S);
         double u0[NU], z1[NS], sl[2 * NY], res[3];
-        int it_dyn;
         const int st_dyn = soft_solve<NS, NU, NY, 64>(S, ws, u0, z1, sl, res, it_dyn);
-        if (st_dyn != kInfeasible) {
-            MPC_UNROLL for (int i = 0; i < NU; i++) u[i] = (DU && P.in_is_du) ? z1[DU ? NX + i : 0] : u0[i];          // :798
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = z1[i];         // :799
-            for (int i = 0; i < 2 * NY; i++) slk[i] = sl[i];               // :800
-        } else {                                                           // :804-805 hold u, propagate the model
-            double xn[NX];
-            MPC_UNROLL for (int i = 0; i < NX; i++) {
-                double v = P.fxc[i];
-                MPC_UNROLL for (int j = 0; j < NX; j++) v += P.Am[i][j] * xh[j];
-                MPC_UNROLL for (int j = 0; j < NU; j++) v += P.Bm[i][j] * u[j];
-                MPC_UNROLL for (int j = 0; j < ND; j++) v += P.Bd[i][j] * dh[j];
-                xn[i] = v;
-            }
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = xn[i];
-        }
-        if (a.U) { MPC_UNROLL for (int i = 0; i < NU; i++) a.U[((size_t)k * NU + i) * Bs + b] = u[i]; }
+        if (st_dyn != kInfeasible) { for (int i = 0; i < 2 * NY; i++) slk[i] = sl[i]; }      // :800
         if (a.SL) { for (int i = 0; i < 2 * NY; i++) a.SL[((size_t)k * 2 * NY + i) * Bs + b] = slk[i]; }
-        if (a.st_dyn) { a.st_dyn[(size_t)k * Bs + b] = st_dyn; a.st_ss[(size_t)k * Bs + b] = st_ss; a.it_dyn[(size_t)k * Bs + b] = it_dyn; a.it_ss[(size_t)k * Bs + b] = it_ss; }
-        // ---- plant (MPC_code.py:813-816) -----------------------------------------------------------
-        {
-            double xn[NXP];
-            plant_next<NXP, NU>(P, x, u, a.pxp + k * NXP, a.t0 + k * a.h, a.h, xn);
-            MPC_UNROLL for (int i = 0; i < NXP; i++) x[i] = xn[i];
-        }
+        lane_accept_or_hold<ND, DU>(P, a, k, b, st_dyn, st_ss, it_dyn, it_ss, u0, z1, u, xh, dh);
+        lane_plant_step(P, a, k, x, u, a.pxp + k * NXP);
     }
-    MPC_UNROLL for (int i = 0; i < NXP; i++) a.x[i * Bs + b] = x[i];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { a.xhat[i * Bs + b] = xh[i]; a.xs[i * Bs + b] = xs[i]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) a.dhat[i * Bs + b] = dh[i];
-    MPC_UNROLL for (int i = 0; i < NU; i++) { a.u[i * Bs + b] = u[i]; a.us[i * Bs + b] = us[i]; }
+    lane_state_store<ND>(a, b, x, xh, dh, u, xs, us);
     for (int i = 0; i < 2 * NY; i++) a.sl_keep[i * Bs + b] = slk[i];
     a.ws_valid[b] = 0;
 }
@@ -589,123 +316,41 @@ __global__ __launch_bounds__(64) void loop_kernel_soft(const DevProblem *__restr
 // The closed loop with model parameters that vary over the horizon (def_px / def_py, MPC_code.py:492-510): at step k the OCP sees
 // px_i = def_px(t_k + i), py_i = def_py(t_k + i), i = 0..N-1 (the reference's indexing: time plus stage index), estimator, target, the
 // stage-0 output test and the hold rule see the first of them (p_x_k, p_y_k: MPC_code.py:500-502,524,693,770-772,804).  Instance per lane
-// like loop_kernel; the OCP is ocp_kernel_pxy's - per-block affine terms and boxes in a slab, rpdip_lane<.., LTV>, cold every step - so a
-// fused run equals the call-by-call one (three C-ABI calls per step with mpc_set_model_offsets) bit for bit.  One instantiation per
-// dimension set (all bounds maskable).
+// like loop_kernel; the OCP is ocp_kernel_pxy's - lane_pxy_slab, rpdip_lane<.., LTV>, cold every step - and estimator and target are the
+// functions kf_kernel and target_kernel run (lane_correct, target_lane), so a fused run equals the call-by-call one (three C-ABI calls per
+// step with mpc_set_model_offsets) bit for bit.  One instantiation per dimension set (all bounds maskable), for sets without user rows of
+// the target.
 template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG>
 __global__ __launch_bounds__(64) void loop_kernel_pxy(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
-    constexpr int NS = NX + (DU ? NU : 0) + NG, NB = NX + (DU ? NU : 0), NE = NX + ND, NC = NS + NU, NLTV = NS * (NS + NU + 1), NLIN = NLTV + 2 * NS;
+    constexpr int NS = NX + (DU ? NU : 0) + NG, NC = NS + NU, NLTV = NS * (NS + NU + 1), NLIN = NLTV + 2 * NS;
     const int lane = threadIdx.x, b = blockIdx.x * 64 + lane;
     if (b >= a.B) return;
     const DevProblem &P = *Pp;
     const size_t Bs = a.Bs;
     const int N = P.N;
     double x[NXP], xh[NX], dh[ND > 0 ? ND : 1], u[NU], xs[NX], us[NU];
-    MPC_UNROLL for (int i = 0; i < NXP; i++) x[i] = a.x[i * Bs + b];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { xh[i] = a.xhat[i * Bs + b]; xs[i] = a.xs[i * Bs + b]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = a.dhat[i * Bs + b];
-    MPC_UNROLL for (int i = 0; i < NU; i++) { u[i] = a.u[i * Bs + b]; us[i] = a.us[i * Bs + b]; }
+    lane_state_load<ND>(a, b, x, xh, dh, u, xs, us);
     StageConst<NS, NU> C;
     load_stage_const<NS, NU, DU>(P, C);
-    constexpr int SL = BlkLayout<NS, NU, NC>::SLOTS;
-    Ws ws{(gv2d *)((v2d *)a.ws + ((size_t)blockIdx.x * (N + 2) + 1) * SL * 64), N, SL, lane};
+    const Ws ws = lane_ws<NS, NU, NC>(a.ws, N);
     double *const lin = a.lin + (size_t)blockIdx.x * N * NLIN * 64 + lane;
     for (int k = 0; k < a.nsteps; k++) {
         const double *pxh = a.px_h ? a.px_h + (size_t)k * N * NX : nullptr, *pyh = a.py_h ? a.py_h + (size_t)k * N * NY : nullptr;
         double px0[NX], py0[NY];
         MPC_UNROLL for (int i = 0; i < NX; i++) px0[i] = pxh ? pxh[i] : 0.0;
         MPC_UNROLL for (int i = 0; i < NY; i++) py0[i] = pyh ? pyh[i] : 0.0;
-        if (a.XP) { MPC_UNROLL for (int i = 0; i < NXP; i++) a.XP[((size_t)k * NXP + i) * Bs + b] = x[i]; }
-        if (a.XHAT) { MPC_UNROLL for (int i = 0; i < NX; i++) a.XHAT[((size_t)k * NX + i) * Bs + b] = xh[i]; }
-        // ---- measure and estimate (MPC_code.py:524-534, 577-668): yhat = Fy_model(xhat, dhat) + p_y_k ----
-        if (P.estimator != MPC_EST_NONE) {
-            double xi[NE], innov[NY];
-            MPC_UNROLL for (int i = 0; i < NX; i++) xi[i] = xh[i];
-            MPC_UNROLL for (int i = 0; i < ND; i++) xi[NX + i] = dh[i];
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                double yh = P.fyc[i] + py0[i], yy = a.pyp[k * NY + i];
-                MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
-                MPC_UNROLL for (int j = 0; j < NXP; j++) yy += P.Cp[i][j] * x[j];
-                innov[i] = (yy + py0[i]) - yh;      // the plant's output carries p_ymp = p_y_k too (MPC_code.py:505-507,534)
-            }
-            if (P.estimator == MPC_EST_KALMAN) {
-                double Pk[NE][NE];
-                MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) Pk[i][j] = a.Pk[(i * NE + j) * Bs + b]; }
-                kalman_lane<NE, NY>(P, xi, Pk, innov);
-                MPC_UNROLL for (int i = 0; i < NE; i++) { MPC_UNROLL for (int j = 0; j < NE; j++) a.Pk[(i * NE + j) * Bs + b] = Pk[i][j]; }
-            } else {
-                MPC_UNROLL for (int i = 0; i < NE; i++) { double s = 0.0; MPC_UNROLL for (int l = 0; l < NY; l++) s += P.Kfix[i][l] * innov[l]; xi[i] += s; }
-            }
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = xi[i];
-            MPC_UNROLL for (int i = 0; i < ND; i++) { double d = xi[NX + i]; if (P.has_dsat) d = dmin(dmax(d, P.dmin[i]), P.dmax[i]); dh[i] = d; }
-        }
-        if (a.DHAT) { MPC_UNROLL for (int i = 0; i < ND; i++) a.DHAT[((size_t)k * ND + i) * Bs + b] = dh[i]; }
-        // ---- target with p_x_k, p_y_k in its equalities (MPC_code.py:693-718), cold like the per-call entry point ----
-        double usp[NU], ysp[NY], xs_n[NX], us_n[NU], ys_n[NY];
-        MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
-        MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
-        int it_ss;
-        // (no user rows of the target here: NGS = NHS = 0 by construction - make_launchers_mode instantiates this loop only for sets without them)
-        const int st_ss = target_lane<NX, NU, NY, ND>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, nullptr, 0, nullptr, pxh ? px0 : nullptr, pyh ? py0 : nullptr);
-        if (st_ss != kInfeasible) {
-            MPC_UNROLL for (int i = 0; i < NX; i++) xs[i] = xs_n[i];
-            MPC_UNROLL for (int i = 0; i < NU; i++) us[i] = us_n[i];
-        }
-        if (a.XS) { MPC_UNROLL for (int i = 0; i < NX; i++) a.XS[((size_t)k * NX + i) * Bs + b] = xs[i]; }
-        if (a.US) { MPC_UNROLL for (int i = 0; i < NU; i++) a.US[((size_t)k * NU + i) * Bs + b] = us[i]; }
-        if (a.YS) {   // ys = Fy_model(xs, us, dhat, p_y_k), MPC_code.py:730
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                double v = P.fyc[i] + py0[i];
-                MPC_UNROLL for (int j = 0; j < NX; j++) v += P.Cm[i][j] * xs[j];
-                MPC_UNROLL for (int j = 0; j < ND; j++) v += P.Cd[i][j] * dh[j];
-                a.YS[((size_t)k * NY + i) * Bs + b] = v;
-            }
-        }
-        // ---- OCP (MPC_code.py:733-805): per-block affine terms and boxes -> slab (as ocp_kernel_pxy) ----
+        lane_log<NXP>(a.XP, k, Bs, b, x);
+        lane_log<NX>(a.XHAT, k, Bs, b, xh);
+        lane_estimate<NY, ND>(P, a, k, b, x, xh, dh, py0);
+        lane_log<ND>(a.DHAT, k, Bs, b, dh);
+        int it_ss, it_dyn;
+        const int st_ss = lane_target<NY, ND, 0, 0>(P, a, k, b, dh, xs, us, it_ss, false, pxh ? px0 : nullptr, pyh ? py0 : nullptr);
+        lane_log_ys<NY, ND>(P, a, k, b, xs, dh, py0);
         OcpInst<NS, NU> q;
         build_inst<NX, NU, NY, ND, DU, NG>(P, xh, xs, us, dh, u, q);
-        double e0[NY];      // output offsets without py
-        MPC_UNROLL for (int i = 0; i < NY; i++) { double e = P.fyc[i]; MPC_UNROLL for (int j = 0; j < ND; j++) e += P.Cd[i][j] * dh[j]; e0[i] = e; }
-        if (P.y_bounded && pyh) {      // the stage-0 row is a test of the given x_0 (Control_Calc.py:128-151), with py_0
-            q.ok0 = true;
-            MPC_UNROLL for (int i = 0; i < NY; i++) {
-                double y0 = e0[i] + py0[i];
-                MPC_UNROLL for (int j = 0; j < NX; j++) y0 += P.Cm[i][j] * xh[j];
-                const double rl = kBoundRelax * dmax(1.0, fabs(P.ymin[i])), rh = kBoundRelax * dmax(1.0, fabs(P.ymax[i]));
-                if (!(y0 >= P.ymin[i] - rl) || !(y0 <= P.ymax[i] + rh)) q.ok0 = false;
-            }
-        }
-        for (int kk = 0; kk < N; kk++) {
-            double *lb = lin + (size_t)kk * NLIN * 64;
-            double pxk[NX];
-            MPC_UNROLL for (int i = 0; i < NX; i++) pxk[i] = pxh ? pxh[(size_t)kk * NX + i] : 0.0;
-            MPC_UNROLL for (int i = 0; i < NS; i++) {
-                MPC_UNROLL for (int j = 0; j < NS; j++) lb[(i * NS + j) * 64] = C.A[i][j];
-                MPC_UNROLL for (int j = 0; j < NU; j++) lb[(NS * NS + i * NU + j) * 64] = C.B[i][j];
-                double c = q.c[i];
-                if (i < NX) c += pxk[i < NX ? i : 0];
-                if (i >= NB) { const int r = P.yg_row[i >= NB ? i - NB : 0]; MPC_UNROLL for (int j = 0; j < NX; j++) c += P.Cm[r][j] * pxk[j]; }
-                lb[(NS * NS + NS * NU + i) * 64] = c;
-            }
-            double lo[NS], hi[NS];
-            const bool end = kk == N - 1;
-            MPC_UNROLL for (int i = 0; i < NS; i++) { lo[i] = end ? P.zlo_e[i] : P.zlo_m[i]; hi[i] = end ? P.zhi_e[i] : P.zhi_m[i]; }
-            if (P.y_bounded && !end) {
-                MPC_UNROLL for (int i = 0; i < NY; i++) {
-                    const double e = e0[i] + (pyh ? pyh[(size_t)(kk + 1) * NY + i] : 0.0);
-                    const double sc = P.ymap_scale[i];
-                    const double aa = (P.ymin[i] - e) / sc, bb = (P.ymax[i] - e) / sc;
-                    const double l = sc > 0 ? aa : bb, hh = sc > 0 ? bb : aa;
-                    const int idx = P.ymap_idx[i];
-                    MPC_UNROLL for (int j = 0; j < NS; j++)
-                        if (j == idx) { lo[j] = dmax(lo[j], l); hi[j] = dmin(hi[j], hh); }
-                }
-            }
-            MPC_UNROLL for (int i = 0; i < NS; i++) { lb[(NLTV + i) * 64] = lo[i]; lb[(NLTV + NS + i) * 64] = hi[i]; }
-        }
+        lane_pxy_slab<NX, NY, ND, DU, NG>(P, C, q, xh, dh, pxh, pyh, 1, lin);
         double u0[NU], z1[NS], res[3];
-        int it_dyn;
         int st_dyn, it_sum = 0;
         for (int pass = 0;; pass++) {
             st_dyn = rpdip_lane<NS, NU, DU, NC, true, true>(P, C, q, ws, P.max_iter, false, 0.0, u0, z1, res, it_dyn, lin, 1, NLIN, NLTV);
@@ -714,33 +359,12 @@ __global__ __launch_bounds__(64) void loop_kernel_pxy(const DevProblem *__restri
         }
         it_dyn = it_sum;
         if (P.term_cons && st_dyn != kInfeasible && term_missed<NS, NU, NC, NX>(P, ws, q)) st_dyn = kInfeasible;
-        if (st_dyn != kInfeasible) {
-            MPC_UNROLL for (int i = 0; i < NU; i++) u[i] = (DU && P.in_is_du) ? z1[DU ? NX + i : 0] : u0[i];          // :798
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = z1[i];         // :799
-        } else {                                                           // :804-805 hold u, propagate the model (with p_x_k)
-            double xn[NX];
-            MPC_UNROLL for (int i = 0; i < NX; i++) {
-                double v = P.fxc[i] + px0[i];
-                MPC_UNROLL for (int j = 0; j < NX; j++) v += P.Am[i][j] * xh[j];
-                MPC_UNROLL for (int j = 0; j < NU; j++) v += P.Bm[i][j] * u[j];
-                MPC_UNROLL for (int j = 0; j < ND; j++) v += P.Bd[i][j] * dh[j];
-                xn[i] = v;
-            }
-            MPC_UNROLL for (int i = 0; i < NX; i++) xh[i] = xn[i];
-        }
-        if (a.U) { MPC_UNROLL for (int i = 0; i < NU; i++) a.U[((size_t)k * NU + i) * Bs + b] = u[i]; }
-        if (a.st_dyn) { a.st_dyn[(size_t)k * Bs + b] = st_dyn; a.st_ss[(size_t)k * Bs + b] = st_ss; a.it_dyn[(size_t)k * Bs + b] = it_dyn; a.it_ss[(size_t)k * Bs + b] = it_ss; }
-        {
-            double xn[NXP], pxpk[NXP];      // the plant's state equation carries p_xmp = p_x_k too (MPC_code.py:500-504,813-816)
-            MPC_UNROLL for (int i = 0; i < NXP; i++) pxpk[i] = a.pxp[k * NXP + i] + ((pxh && i < NX) ? px0[i < NX ? i : 0] : 0.0);
-            plant_next<NXP, NU>(P, x, u, pxpk, a.t0 + k * a.h, a.h, xn);
-            MPC_UNROLL for (int i = 0; i < NXP; i++) x[i] = xn[i];
-        }
+        lane_accept_or_hold<ND, DU>(P, a, k, b, st_dyn, st_ss, it_dyn, it_ss, u0, z1, u, xh, dh, px0);
+        double pxpk[NXP];      // the plant's state equation carries p_xmp = p_x_k too (MPC_code.py:500-504,813-816)
+        MPC_UNROLL for (int i = 0; i < NXP; i++) pxpk[i] = a.pxp[k * NXP + i] + ((pxh && i < NX) ? px0[i < NX ? i : 0] : 0.0);
+        lane_plant_step(P, a, k, x, u, pxpk);
     }
-    MPC_UNROLL for (int i = 0; i < NXP; i++) a.x[i * Bs + b] = x[i];
-    MPC_UNROLL for (int i = 0; i < NX; i++) { a.xhat[i * Bs + b] = xh[i]; a.xs[i * Bs + b] = xs[i]; }
-    MPC_UNROLL for (int i = 0; i < ND; i++) a.dhat[i * Bs + b] = dh[i];
-    MPC_UNROLL for (int i = 0; i < NU; i++) { a.u[i * Bs + b] = u[i]; a.us[i * Bs + b] = us[i]; }
+    lane_state_store<ND>(a, b, x, xh, dh, u, xs, us);
     a.ws_valid[b] = 0;      // (this kernel's workspace layout is not a warm start for the others)
 }
 

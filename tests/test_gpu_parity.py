@@ -800,7 +800,7 @@ def test_model_parameters_over_the_horizon(pkg, solver_factory):
 
 def test_fused_closed_loop_with_the_user_plant(nlplant, xp_nlplant):
     """Ex_LMPC_nlplant / Ex_LMPCxp_nlplant: linear controller, the Ex-file's own plant function as the process.  The function is
-    traced and compiled into the problem's own library (capi.Solver, nlcodegen.emit_plant_header; mpc_amd.hip:plant_next integrates it
+    traced and compiled into the problem's own library (capi.Solver, nlcodegen.emit_plant_header; mpc_lane_step.hpp:plant_next integrates it
     with Mx RK4 steps), so the whole loop runs in one kernel; it must equal the call-by-call mode with the plant on the host, which
     tests above pin to the oracle.  Both models are open-loop unstable (|A^32| > 1e4): the library then picks the instance-per-lane
     kernel and cold starts, and differences between two runs grow about threefold per step, hence 12 steps."""
