@@ -181,12 +181,20 @@ int mpc_loop_set_schedule(mpc_handle *h, int32_t nsteps, const double *ysp, cons
  * With a schedule set mpc_loop_run uses the instance-per-lane loop with per-block stage data, target and OCP cold at every step: the same numbers
  * as the call-by-call sequence mpc_set_model_offsets / mpc_kf_update / mpc_target_solve / mpc_ocp_solve(px, py). */
 int mpc_loop_set_model_schedule(mpc_handle *h, int32_t nsteps, const double *px, const double *py);
+/* White noise of the loop (R_wn, G_wn / Q_wn: MPC_code.py:537-541, 822-827), per step and per instance, the caller's draws: v [nsteps][B][ny] or NULL,
+ * w [nsteps][B][nxp] or NULL; both NULL: off.  Step k of the arrays is step k of the schedule (the k0 of mpc_loop_run).  The measurement that enters the
+ * innovation becomes Cp x_k + pyp_k (+ p_y_k) + v_k, the plant state Fx_p(...) + w_k (linear and compiled user plant alike); the log "Xp" stays the state
+ * that was measured, so Xp[k] includes w_{k-1}.  Valid after mpc_loop_alloc, which clears the noise; mpc_loop_set_state does not touch it.  The call drains
+ * the handle's stream before it overwrites a buffer.  Returns -1 for nsteps outside 1..max_steps, -8 for v on a handle with MPC_EST_NONE (nothing reads
+ * the measurement) - either leaves the noise that was in force untouched; mpc_loop_run over steps beyond the noise's nsteps returns -1. */
+int mpc_loop_set_noise(mpc_handle *h, int32_t nsteps, const double *v, const double *w);
 int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps);
 int mpc_loop_sync(mpc_handle *h);
 int mpc_loop_get_log(mpc_handle *h, const char *name, void *out);
 
 /* Convenience wrapper with host buffers only (set_state, set_schedule, run, sync, get_state):
- * the fused equivalent of calling the three solvers nsteps times from MPC_code.py's loop. */
+ * the fused equivalent of calling the three solvers nsteps times from MPC_code.py's loop.  It runs with whatever noise is in force
+ * (mpc_loop_set_noise; none after the mpc_loop_alloc it makes itself when the batch, the steps or the log level do not fit). */
 int mpc_closed_loop(mpc_handle *h, int32_t B, int32_t nsteps, double *x_p, double *xhat, double *dhat,
                     double *P, double *u, double *xs, double *us, const double *ysp, const double *usp,
                     const double *xsp, const double *pxp, const double *pyp, double *U_log /* [nsteps][B][nu] or NULL */);

@@ -181,6 +181,7 @@ def load_library(path: Optional[str] = None) -> ct.CDLL:
     lib.mpc_loop_get_state.argtypes = [ct.c_void_p] + [_dp] * 7
     lib.mpc_loop_set_schedule.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 5
     lib.mpc_loop_set_model_schedule.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 2
+    lib.mpc_loop_set_noise.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 2
     lib.mpc_ocp_solve.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 7 + [_dp, _dp, _dp, _ip, _ip, _dp]
     lib.mpc_target_solve.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 5 + [_dp, _dp, _dp, _ip, _ip]
     lib.mpc_kf_update.argtypes = [ct.c_void_p, ct.c_int32, _dp, _dp, _dp]
@@ -203,7 +204,7 @@ def load_library(path: Optional[str] = None) -> ct.CDLL:
 
 
 EXPORTS = ("mpc_lin_create", "mpc_destroy", "mpc_last_error", "mpc_ocp_solve", "mpc_get_slacks", "mpc_target_solve", "mpc_kf_update", "mpc_set_model_offsets",
-           "mpc_loop_alloc", "mpc_loop_set_state", "mpc_loop_get_state", "mpc_loop_set_schedule", "mpc_loop_set_model_schedule", "mpc_loop_run",
+           "mpc_loop_alloc", "mpc_loop_set_state", "mpc_loop_get_state", "mpc_loop_set_schedule", "mpc_loop_set_model_schedule", "mpc_loop_set_noise", "mpc_loop_run",
            "mpc_loop_sync", "mpc_loop_get_log", "mpc_closed_loop", "mpc_last_kernel_ms", "mpc_stream", "mpc_dev_ptr",
            "mpc_pack_u", "mpc_pack_log", "mpc_set_option", "mpc_get_option", "mpc_build_info",
            "mpc_comm_unique_id", "mpc_comm_init", "mpc_comm_destroy", "mpc_comm_rank", "mpc_comm_allgather",
@@ -491,6 +492,18 @@ class Solver:
         n = 0 if pxa is None and pya is None else len(pxa if pxa is not None else pya)
         self._msched_keep = (pxa, pya)
         self._chk(self.lib.mpc_loop_set_model_schedule(self.h, int(n), _p(pxa), _p(pya)), "mpc_loop_set_model_schedule")
+
+    def loop_set_noise(self, v=None, w=None):
+        """white noise of the resident loop: ``v`` [nsteps, B, ny] on the measurements, ``w`` [nsteps, B, nxp] on the plant state after its step
+        (``MPC_code.py:537-541, 822-827``), step k of the arrays being step k of the schedule; both ``None``: none"""
+        arrs = [None if a is None else _c(a) for a in (v, w)]
+        for a, d in zip(arrs, (self.p.ny, self.p.nxp)):
+            if a is not None and (a.ndim != 3 or a.shape[1:] != (self._loop_B, d)):
+                raise ValueError(f"noise: [nsteps, {self._loop_B}, {d}] expected, got {a.shape}")
+        n = next((a.shape[0] for a in arrs if a is not None), 0)
+        if any(a is not None and a.shape[0] != n for a in arrs):
+            raise ValueError("noise: v and w cover the same number of steps")
+        self._chk(self.lib.mpc_loop_set_noise(self.h, int(n), _p(arrs[0]), _p(arrs[1])), "mpc_loop_set_noise")
 
     def loop_run(self, k0: int, nsteps: int):
         self._chk(self.lib.mpc_loop_run(self.h, int(k0), int(nsteps)), "mpc_loop_run")

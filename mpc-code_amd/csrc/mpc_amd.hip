@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64) void loop_kernel(const DevProblem *__restrict__
         if (P.term_cons && st_dyn != kInfeasible && term_missed<NS, NU, NC, NX>(P, ws, q)) st_dyn = kInfeasible;
         ws_valid = st_dyn == kSolved;
         lane_accept_or_hold<ND, DU>(P, a, k, b, st_dyn, st_ss, it_dyn, it_ss, u0, z1, u, xh, dh);
-        lane_plant_step(P, a, k, x, u, a.pxp + k * NXP);
+        lane_plant_step(P, a, k, b, x, u, a.pxp + k * NXP);
     }
     lane_state_store<ND>(a, b, x, xh, dh, u, xs, us);
     a.ws_valid[b] = ws_valid ? 1 : 0;
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(64) void loop_kernel_soft(const DevProblem *__restr
         if (st_dyn != kInfeasible) { for (int i = 0; i < 2 * NY; i++) slk[i] = sl[i]; }      // :800
         if (a.SL) { for (int i = 0; i < 2 * NY; i++) a.SL[((size_t)k * 2 * NY + i) * Bs + b] = slk[i]; }
         lane_accept_or_hold<ND, DU>(P, a, k, b, st_dyn, st_ss, it_dyn, it_ss, u0, z1, u, xh, dh);
-        lane_plant_step(P, a, k, x, u, a.pxp + k * NXP);
+        lane_plant_step(P, a, k, b, x, u, a.pxp + k * NXP);
     }
     lane_state_store<ND>(a, b, x, xh, dh, u, xs, us);
     for (int i = 0; i < 2 * NY; i++) a.sl_keep[i * Bs + b] = slk[i];
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(64) void loop_kernel_pxy(const DevProblem *__restri
         lane_accept_or_hold<ND, DU>(P, a, k, b, st_dyn, st_ss, it_dyn, it_ss, u0, z1, u, xh, dh, px0);
         double pxpk[NXP];      // the plant's state equation carries p_xmp = p_x_k too (MPC_code.py:500-504,813-816)
         MPC_UNROLL for (int i = 0; i < NXP; i++) pxpk[i] = a.pxp[k * NXP + i] + ((pxh && i < NX) ? px0[i < NX ? i : 0] : 0.0);
-        lane_plant_step(P, a, k, x, u, pxpk);
+        lane_plant_step(P, a, k, b, x, u, pxpk);
     }
     lane_state_store<ND>(a, b, x, xh, dh, u, xs, us);
     a.ws_valid[b] = 0;      // (this kernel's workspace layout is not a warm start for the others)
@@ -421,6 +421,7 @@ __global__ __launch_bounds__(64 * NW) void loop_kernel_tp(const DevProblem *__re
                 MPC_UNROLL for (int i = 0; i < ND; i++) xi[NX + i] = dh[i];
                 MPC_UNROLL for (int i = 0; i < NY; i++) {
                     double yh = P.fyc[i], yy = a.pyp[k * NY + i];
+                    if (a.vn) yy += (a.vn + (size_t)((size_t)k * NY + i) * Bs)[bq];      // white noise on the measurement (wave 1's half of the filter is the covariance alone: it sees no y)
                     MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
                     MPC_UNROLL for (int j = 0; j < NXP; j++) yy += P.Cp[i][j] * x[j];
                     innov[i] = yy - yh;
@@ -539,6 +540,7 @@ __global__ __launch_bounds__(64 * NW) void loop_kernel_tp(const DevProblem *__re
             if (a.st_dyn) { (a.st_dyn + (size_t)k * Bs)[bq] = st_dyn; (a.it_dyn + (size_t)k * Bs)[bq] = it_dyn; }
             double xn[NXP];
             plant_next<NXP, NU>(P, x, u, a.pxp + k * NXP, a.t0 + k * a.h, a.h, xn);
+            if (a.wn) { MPC_UNROLL for (int i = 0; i < NXP; i++) xn[i] += (a.wn + (size_t)((size_t)k * NXP + i) * Bs)[bq]; }      // :822-827
             MPC_UNROLL for (int i = 0; i < NXP; i++) (a.x + (size_t)(i) * Bs)[bq] = xn[i];
             MPC_UNROLL for (int i = 0; i < NX; i++) (a.xhat + (size_t)(i) * Bs)[bq] = xh[i];
             MPC_UNROLL for (int i = 0; i < NU; i++) (a.u + (size_t)(i) * Bs)[bq] = u[i];
@@ -608,8 +610,12 @@ struct WvKernelCfg {
     static constexpr int ni() { return NI; }
 };
 
-template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS = 0, int NHS = 0>
-__global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__restrict__ Pp, LoopArgs a)
+// The body of the two entries below.  NOISE: the white noise a.vn / a.wn of mpc_loop_set_noise is read.  A compile-time switch, and a second entry, because the
+// noise-free loop is the benchmark's and its kernel sits at the register limit: a wave-uniform null test on the two pointers inside the one kernel fitted (256 VGPRs,
+// no scratch) but cost the noise-free headline 0.9 % on an MI355X, this form nothing (profiles/lin_noise_cost.txt).  The price is the build: every instantiation of
+// the wave kernel compiles twice.
+template <bool NOISE, int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS, int NHS>
+__device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, const LoopArgs &a)
 {
     using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
     using Cfg = typename KC::Cfg;
@@ -673,7 +679,7 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
             }
             double xi_old = 0.0, xi_new = 0.0;
             if (P.estimator != MPC_EST_NONE)
-                kalman_row16<NX, NY, ND, NXP, NU>(P, r16, b16 < NI, kq, KC::K_X, KC::K_XH, KC::K_P, a.pyp + k * NY, tab, T + b16c * RT::XCH, xi_old, xi_new);
+                kalman_row16<NX, NY, ND, NXP, NU>(P, r16, b16 < NI, kq, KC::K_X, KC::K_XH, KC::K_P, a.pyp + k * NY, (NOISE && a.vn) ? a.vn + (size_t)k * NY * Bs + bi : nullptr, Bs, tab, T + b16c * RT::XCH, xi_old, xi_new);
             if (inst16 && a.DHAT && r16 >= NX && r16 < NE) (a.DHAT + (size_t)((size_t)k * ND + (r16 - NX)) * Bs)[bi] = xi_new;
             double delta = row16_max(r16 < NE ? fabs(xi_new - xi_old) : 0.0);      // warm-start test: estimate against its prediction
             __syncthreads();
@@ -720,6 +726,7 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
                     MPC_UNROLL for (int i = 0; i < ND; i++) xi[NX + i] = dh[i];
                     MPC_UNROLL for (int i = 0; i < NY; i++) {
                         double yh = P.fyc[i], yy = a.pyp[k * NY + i];
+                        if (NOISE && a.vn) yy += (a.vn + (size_t)((size_t)k * NY + i) * Bs)[bq];
                         MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
                         MPC_UNROLL for (int j = 0; j < NXP; j++) yy += P.Cp[i][j] * x[j];
                         innov[i] = yy - yh;
@@ -846,6 +853,7 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
             {
                 double xn[NXP];
                 plant_next<NXP, NU>(P, x, u, a.pxp + k * NXP, a.t0 + k * a.h, a.h, xn);
+                if (NOISE && a.wn) { MPC_UNROLL for (int i = 0; i < NXP; i++) xn[i] += (a.wn + (size_t)((size_t)k * NXP + i) * Bs)[bq]; }      // :822-827
                 MPC_UNROLL for (int i = 0; i < NXP; i++) kp[KC::K_X + i] = xn[i];
             }
             MPC_UNROLL for (int i = 0; i < NX; i++) kp[KC::K_XH + i] = xh[i];
@@ -869,6 +877,19 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
         MPC_UNROLL for (int i = 0; i < NU; i++) rows[i * 64 + lane] = a_get(X[j].u[i]);
         MPC_UNROLL for (int i = 0; i < NC; i++) { rows[(NU + i) * 64 + lane] = a_get(X[j].ll[i]); rows[(NU + NC + i) * 64 + lane] = a_get(X[j].lh[i]); }
     }
+}
+
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS = 0, int NHS = 0>
+__global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__restrict__ Pp, LoopArgs a)
+{
+    loop_wv_body<false, NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>(Pp, a);
+}
+
+// ... and with the white noise: launched when a noise array is in force (another name, so that a listing's noise-free kernel is found by the name it always had)
+template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS = 0, int NHS = 0>
+__global__ __launch_bounds__(64, 1) void loop_noisy_wv_kernel(const DevProblem *__restrict__ Pp, LoopArgs a)
+{
+    loop_wv_body<true, NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>(Pp, a);
 }
 
 // One solver(...) call per instance (MPC_code.py:776-781) on the wave-autonomous solver: the per-call entry point mpc_ocp_solve.
@@ -1022,11 +1043,12 @@ template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool
 static int launch_loop_wv(const DevProblem *p, LoopArgs a, hipStream_t s, int dev)
 {
     using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
-    auto kern = loop_kernel_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
-    static bool attr_set[64] = {};      // per device: more than 64 KB of dynamic LDS has to be asked for
-    if (!attr_set[dev]) {
+    const bool noisy = a.vn || a.wn;      // (the entry whose body reads the noise arrays; the noise-free loop runs the one compiled without them)
+    auto kern = noisy ? loop_noisy_wv_kernel<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS> : loop_kernel_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
+    static bool attr_set[2][64] = {};      // per entry and device: more than 64 KB of dynamic LDS has to be asked for
+    if (!attr_set[noisy][dev]) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)KC::lds_bytes(64)) != hipSuccess) return -1;
-        attr_set[dev] = true;
+        attr_set[noisy][dev] = true;
     }
     hipLaunchKernelGGL(kern, dim3((a.B + NI - 1) / NI), dim3(64), KC::lds_bytes(a.N), s, p, a);
     return 0;
@@ -1193,6 +1215,7 @@ struct mpc_handle {
     DevBuf soft_ws, soft_sl, soft_keep; int soft_B = 0;      // soft output constraints: the arrowhead solver's workspace, the last call's optimal slacks
     DevBuf pxy_in, pxy_lin, pxy_ws, off_px, off_py; int off_B = 0; bool off_has_px = false, off_has_py = false;
     DevBuf msch; int msch_steps = 0; bool msch_px = false, msch_py = false;      // def_px / def_py over the horizon for every step of the fused loop
+    DevBuf noise_v, noise_w; int noise_steps = 0; bool has_vn = false, has_wn = false;      // white noise of the resident loop (mpc_loop_set_noise), [step][ny][Bs] / [step][nxp][Bs]
     DevBuf st_x, st_xhat, st_dhat, st_P, st_u, st_xs, st_us, st_flag, st_Kg, st_Pn, st_tw, sch;
     LogTab log;                 // the logs mpc_loop_alloc enabled
     mpc_comm::State comm;       // multi-GPU (one process per GPU): the ranks of the job, staging buffers of the collectives
@@ -1520,6 +1543,7 @@ extern "C" void mpc_destroy(mpc_handle *h)
     h->pc_prev.release(); h->pc_valid.release(); h->pc_guess.release(); h->pc_traj.release();
     h->soft_ws.release(); h->soft_sl.release(); h->soft_keep.release();
     h->pxy_in.release(); h->pxy_lin.release(); h->pxy_ws.release(); h->off_px.release(); h->off_py.release(); h->msch.release();
+    h->noise_v.release(); h->noise_w.release();
     for (DevBuf *b : {&h->scratch, &h->ws, &h->st_x, &h->st_xhat, &h->st_dhat, &h->st_P, &h->st_u, &h->st_xs, &h->st_us, &h->st_flag, &h->st_Kg, &h->st_Pn, &h->st_tw, &h->sch}) b->release();
     if (h->dp) (void)hipFree(h->dp);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1943,6 +1967,7 @@ extern "C" int mpc_loop_alloc(mpc_handle *h, int32_t B, int32_t max_steps, int32
         HIP_TRY(hipMemsetAsync(b->p, 0, b->bytes, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->state_set = false; h->msch_steps = 0; h->msch_px = h->msch_py = false;
+    h->noise_steps = 0; h->has_vn = h->has_wn = false;
     if (ensure_ws(h, Bs)) return -10;
     const int sdim = P.ny + P.nu + P.nxp + P.ny;   // ysp usp pxp pyp
     if (h->sch.ensure((size_t)max_steps * sdim * 8)) return -10;
@@ -2064,6 +2089,34 @@ extern "C" int mpc_loop_set_model_schedule(mpc_handle *h, int32_t nsteps, const 
     return 0;
 }
 
+// White noise of the resident loop (MPC_code.py:537-541, 822-827): v [nsteps][B][ny] on the measurement, w [nsteps][B][nxp] on the plant state after its
+// step, the caller's draws; either may be NULL, both NULL switch the noise off.  Step k of the arrays is step k of the schedule.  The stream is drained
+// first: a launch in flight may still read the buffers.
+extern "C" int mpc_loop_set_noise(mpc_handle *h, int32_t nsteps, const double *v, const double *w)
+{
+    if (!h || h->B == 0) return fail(-1, "mpc_loop_alloc first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const DevProblem &P = h->hp;
+    if (v || w) {      // a refused call leaves the noise that was in force as it is
+        if (nsteps < 1 || nsteps > h->max_steps) return fail(-1, "noise for %d steps, %d allocated", nsteps, h->max_steps);
+        if (v && P.estimator == MPC_EST_NONE) return fail(-8, "measurement noise on a problem without estimator (MPC_EST_NONE): nothing reads the measurement");
+    }
+    h->noise_steps = 0; h->has_vn = h->has_wn = false;      // (a HIP failure below leaves it off)
+    if (!v && !w) return 0;
+    auto put = [&](DevBuf &buf, const double *src, int dim) -> int {
+        std::vector<double> st((size_t)nsteps * dim * h->Bs);
+        steps_to_soa(src, nsteps, h->B, dim, h->Bs, st.data());
+        if (buf.ensure(st.size() * 8)) return -10;
+        HIP_TRY(hipMemcpy(buf.p, st.data(), st.size() * 8, hipMemcpyHostToDevice));
+        return 0;
+    };
+    if (v) { if (int rc = put(h->noise_v, v, P.ny)) return rc; h->has_vn = true; }
+    if (w) { if (int rc = put(h->noise_w, w, P.nxp)) return rc; h->has_wn = true; }
+    h->noise_steps = nsteps;
+    return 0;
+}
+
 // Which closed-loop kernel: 1 = one instance per lane (loop_kernel; fills the chip from about 65536 instances),
 // 2 = horizon-parallel (loop_kernel_tp; one wave per instance, for batches that leave the chip idle otherwise).
 static int loop_mode(const mpc_handle *h)
@@ -2097,6 +2150,8 @@ extern "C" int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps)
         if (h->pxy_lin.ensure(N * h->L.pxy_lin * Bs * sizeof(double)) || h->pxy_ws.ensure((size_t)h->L.pxy_ws_rows * (N + 2) * Bs * sizeof(double))) return -10;
     }
     if (pxy && P.soft) return fail(-8, "soft constraints with horizon parameters (def_px / def_py) are not carried");
+    const bool noisy = h->has_vn || h->has_wn;
+    if (noisy && k0 + nsteps > h->noise_steps) return fail(-1, "steps [%d,%d) outside the noise of %d steps", k0, k0 + nsteps, h->noise_steps);
     const int mode = pxy ? 5 : (P.soft ? 6 : loop_mode(h));
     if (mode != h->ws_mode) {      // the workspace holds another layout (or a per-call solve used it): next OCPs start cold
         HIP_TRY(hipMemsetAsync(h->st_flag.p, 0, 3 * Bs * 4, h->stream));
@@ -2111,6 +2166,8 @@ extern "C" int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps)
         a.u = (double *)h->st_u.p; a.xs = (double *)h->st_xs.p; a.us = (double *)h->st_us.p;
         a.ysp = sch + (size_t)k * P.ny; a.usp = sch + ms * P.ny + (size_t)k * P.nu;
         a.pxp = sch + ms * (P.ny + P.nu) + (size_t)k * P.nxp; a.pyp = sch + ms * (P.ny + P.nu + P.nxp) + (size_t)k * P.ny;
+        a.vn = h->has_vn ? (const double *)h->noise_v.p + (size_t)k * P.ny * Bs : nullptr;
+        a.wn = h->has_wn ? (const double *)h->noise_w.p + (size_t)k * P.nxp * Bs : nullptr;
         auto dl = [&](const char *nm) -> double * { return (double *)h->log.dev(nm, k); };      // (nullptr: a log that is not enabled)
         auto il = [&](const char *nm) -> int32_t * { return (int32_t *)h->log.dev(nm, k); };
         a.U = dl("U"); a.XHAT = dl("X_HAT"); a.XS = dl("XS"); a.US = dl("US"); a.YS = dl("YS"); a.XP = dl("Xp"); a.DHAT = dl("D_HAT");

@@ -56,6 +56,11 @@ static void to_soa(const double *src, int B, int d, size_t Bs, double *dst)
         for (size_t b = B; b < Bs; b++) row[b] = 0.0;
     }
 }
+// host [nsteps][B][d] -> staging [step][d][Bs]: per-instance values of every step of a resident loop (its white noise), step by step through to_soa
+static void steps_to_soa(const double *src, int nsteps, int B, int d, size_t Bs, double *dst)
+{
+    for (int k = 0; k < nsteps; k++) to_soa(src + (size_t)k * B * d, B, d, Bs, dst + (size_t)k * d * Bs);
+}
 static void from_soa(const double *src, int B, int d, size_t Bs, double *dst)
 {
     for (int i = 0; i < d; i++) {

@@ -45,6 +45,8 @@ struct LoopArgs {
     const double *px_h, *py_h;                       // def_px / def_py over the horizon, [step][N][nx] / [step][N][ny] offset to k0 (loop_kernel_pxy), or nullptr
     double *lin;                                     // loop_kernel_pxy: slab of per-block stage data
     double *SL, *soft_ws, *sl_keep;                  // loop_kernel_soft: log of the slacks [step][2 ny][Bs] offset to k0 (or nullptr), the arrowhead solver's workspace, the last accepted slacks [2 ny][Bs]
+    const double *vn, *wn;                           // white noise per step and instance (mpc_loop_set_noise), [step][ny][Bs] on the measurement and [step][nxp][Bs] on the
+                                                     // plant state after its step, offset to k0; nullptr: none (MPC_code.py:537-541, 822-827).  Last: the fields above keep their places
 };
 
 namespace mpc {
@@ -128,7 +130,7 @@ __device__ __forceinline__ void lane_correct(const PT &P, double *Pk_g, size_t B
     }
 }
 
-// One step of the estimator on the plant's output y = Cp x + pyp_k: innovation, correction, saturation of the disturbance estimate.
+// One step of the estimator on the plant's output y = Cp x + pyp_k (+ v_k, the white noise a.vn): innovation, correction, saturation of the disturbance estimate.
 // py0 (or nullptr): p_y_k of the def_py schedule, in the model's output and in the plant's (p_ymp = p_y_k, MPC_code.py:505-507,534).
 template <int NY, int ND, int NXP, int NX, class PT>
 __device__ __forceinline__ void lane_estimate(const PT &P, const LoopArgs &a, int k, int b, const double (&x)[NXP], double (&xh)[NX], double *dh, const double *py0 = nullptr)
@@ -140,6 +142,7 @@ __device__ __forceinline__ void lane_estimate(const PT &P, const LoopArgs &a, in
     MPC_UNROLL for (int i = 0; i < ND; i++) xi[NX + i] = dh[i];
     MPC_UNROLL for (int i = 0; i < NY; i++) {
         double yh = py0 ? P.fyc[i] + py0[i] : P.fyc[i], yy = a.pyp[k * NY + i];
+        if (a.vn) yy += a.vn[((size_t)k * NY + i) * a.Bs + b];
         MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
         MPC_UNROLL for (int j = 0; j < NXP; j++) yy += P.Cp[i][j] * x[j];
         innov[i] = py0 ? (yy + py0[i]) - yh : yy - yh;
@@ -281,12 +284,13 @@ __device__ __forceinline__ void lane_accept_or_hold(const PT &P, const LoopArgs 
     if (a.st_dyn) { a.st_dyn[(size_t)k * Bs + b] = st_dyn; a.st_ss[(size_t)k * Bs + b] = st_ss; a.it_dyn[(size_t)k * Bs + b] = it_dyn; a.it_ss[(size_t)k * Bs + b] = it_ss; }
 }
 
-// ---- plant (MPC_code.py:813-816): x <- x_p(t_k + h); pxp_k is the caller's (the def_px loop adds p_x_k to the schedule's) --------------
+// ---- plant (MPC_code.py:813-816, 822-827): x <- x_p(t_k + h) (+ w_k, the white noise a.wn); pxp_k is the caller's (the def_px loop adds p_x_k to the schedule's) ----
 template <int NXP, int NU, class PT>
-__device__ __forceinline__ void lane_plant_step(const PT &P, const LoopArgs &a, int k, double (&x)[NXP], const double (&u)[NU], const double *pxp_k)
+__device__ __forceinline__ void lane_plant_step(const PT &P, const LoopArgs &a, int k, int b, double (&x)[NXP], const double (&u)[NU], const double *pxp_k)
 {
     double xn[NXP];
     plant_next<NXP, NU>(P, x, u, pxp_k, a.t0 + k * a.h, a.h, xn);
+    if (a.wn) { MPC_UNROLL for (int i = 0; i < NXP; i++) xn[i] += a.wn[((size_t)k * NXP + i) * a.Bs + b]; }
     MPC_UNROLL for (int i = 0; i < NXP; i++) x[i] = xn[i];
 }
 

@@ -989,9 +989,11 @@ __device__ __forceinline__ void row16_fill_tables(const PT &P, double *tab, int 
 // Estimator step (MPC_code.py:524-534, 577-668; kalman(): Estimator.py:297-309): xi = [xhat; dhat] at kp[xi_off + r], plant state at
 // kp[x_off..], covariance rows at kp[p_off + r * NE ..].  On return lane r < NE holds xi_old / xi_new of its row (also written back).
 // slot_on: this lane's instance slot exists (lanes of unused slots compute along on slot 0's data and write nothing).
+// vn_k (or nullptr): this instance's white noise on the measurement at this step, component i at vn_k[i * Bs] (the sixteen lanes of an instance read the same words;
+// lanes of unused slots read slot 0's instance, a wave's instances beyond the batch the zero padding).
 template <int NX, int NY, int ND, int NXP, int NU, class PT>
 __device__ __forceinline__ void kalman_row16(const PT &P, int r, bool slot_on, double *kp, int x_off, int xi_off, int p_off, const double *pyp_k,
-                                             const double *tab, double *xch, double &xi_old, double &xi_new)
+                                             const double *vn_k, size_t Bs, const double *tab, double *xch, double &xi_old, double &xi_new)
 {
     using RT = Row16Tab<NX, NU, NY, ND>;
     constexpr int NE = RT::NE;
@@ -1002,6 +1004,7 @@ __device__ __forceinline__ void kalman_row16(const PT &P, int r, bool slot_on, d
     MPC_UNROLL for (int i = 0; i < NE; i++) xi[i] = kp[xi_off + i];
     MPC_UNROLL for (int i = 0; i < NY; i++) {       // yhat = Fy_model(xhat, dhat) :524, y = Fy_p(x) + pyp :531-534
         double yh = P.fyc[i], yy = pyp_k[i];
+        if (vn_k) yy += vn_k[i * Bs];
         MPC_UNROLL for (int j = 0; j < NE; j++) yh += P.Ca[i][j] * xi[j];
         MPC_UNROLL for (int j = 0; j < NXP; j++) yy += P.Cp[i][j] * kp[x_off + j];
         innov[i] = yy - yh;

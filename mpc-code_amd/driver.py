@@ -21,6 +21,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import capi
+from .noise import loop_noise
 from .shard import allgather_rows, shard_bounds
 
 
@@ -28,10 +29,24 @@ def _bcast(v, B, d):
     return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1, d) if np.ndim(v) > 1 else np.asarray(v, dtype=np.float64), (B, d)))
 
 
+def shard_noise(problem, nsteps: int, B: int, seed: int, total: Optional[int] = None, rank: int = 0, world: int = 1):
+    """The white noises ``V_WN [nsteps, B, ny]``, ``W_WN [nsteps, B, nxp]`` (``noise.loop_noise``; None where the example defines none) of this rank's ``B``
+    instances.  With ``total`` the draws are made for the whole batch and this rank's block (``shard_bounds``) is cut out: a run does not depend on the number of ranks."""
+    if total is None:
+        return loop_noise(problem, nsteps, B, seed)
+    lo, hi = shard_bounds(int(total), world, rank)
+    if hi - lo != B:
+        raise ValueError(f"rank {rank} of {world} owns {hi - lo} of {total} instances but runs {B}")
+    return tuple(None if a is None else np.ascontiguousarray(a[:, lo:hi]) for a in loop_noise(problem, nsteps, int(total), seed))
+
+
 def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None, solver: Optional[capi.Solver] = None,
                     fused: bool = True, device: int = 0, gather: bool = False, total: Optional[int] = None, comm=None,
-                    warm_start: bool = False) -> Dict[str, np.ndarray]:
-    """``gather=True``: this rank ran its shard of a batch of ``total`` instances; every result array is all-gathered over the
+                    warm_start: bool = False, noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """``noise_seed``: the example's white noises ``R_wn`` on every measurement and ``G_wn`` / ``Q_wn`` on the plant state after its step
+    (``MPC_code.py:537-541, 822-827``; unseeded there), one draw per step and instance from ``numpy.random.default_rng(noise_seed)`` (:func:`shard_noise`); on the device
+    through ``mpc_loop_set_noise``, on the host in the call-by-call mode.  ``Yp`` includes the measurement's noise; the draws come back as ``V_WN`` / ``W_WN``.
+    ``gather=True``: this rank ran its shard of a batch of ``total`` instances; every result array is all-gathered over the
     ranks of ``comm`` (mpc-code_amd/shard.py).  ``total`` is required then: a shard does not know the size of the whole.
     ``warm_start`` (call-by-call mode): hand ``mpc_ocp_solve`` the shifted previous optimum as the reference hands it to IPOPT
     (``MPC_code.py:740-764``) and let it keep its multipliers between calls (``ocp_warm_start``); the fused loop always does."""
@@ -42,8 +57,15 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
     B = x0_p.shape[0]
     own = solver is None
     s = capi.Solver(p, device=device) if own else solver
+    noise_set = False
     try:
         sched = p.schedules(nsteps)
+        vn = wn = None
+        if noise_seed is not None:
+            in_job = gather and total is not None and comm is not None
+            vn, wn = shard_noise(p, nsteps, B, noise_seed, total if gather else None, comm.rank if in_job else 0, comm.world if in_job else 1)
+            if vn is not None and p.estimator == "none":      # in both modes, as mpc_loop_set_noise does (-8): nothing would read the noisy measurement
+                raise ValueError("noise_seed: R_wn on a problem without estimator - nothing reads the measurement; leave R_wn out (G_wn / Q_wn alone are taken)")
         if fused and not p.plant_is_linear and not getattr(s, "fused_plant", False):
             raise ValueError("this solver's library has no compiled plant function (User_fxp_Cont): the plant is simulated on the host, "
                              "call run_closed_loop(..., fused=False)")
@@ -59,6 +81,9 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
                 py0 = np.stack([h_[1][0] for h_ in hp])              # p_y_k (zeros without def_py)
             else:
                 s.loop_set_model_schedule(None, None)
+            if noise_seed is not None:      # (without a seed the loop is noise-free, on a caller-owned solver too: the loop_alloc above cleared what its caller had installed)
+                s.loop_set_noise(vn, wn)
+                noise_set = True
             s.loop_run(0, nsteps)
             s.loop_sync()
             out = {k: s.loop_get_log(k) for k in ("U", "X_HAT", "XS", "US", "YS", "Xp", "D_HAT", "STATUS_DYN",
@@ -66,6 +91,8 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
             if getattr(p, "slacks", False):
                 out["Sl"] = s.loop_get_log("SL")                     # :800,808-809 (csrc/mpc_amd.hip:loop_kernel_soft)
             out["Yp"] = out["Xp"] @ p.Cp.T + sched["pyp"][:nsteps, None, :] + py0[:, None, :]                 # :531-534 (p_ymp = p_y_k, :505-507)
+            if vn is not None:
+                out["Yp"] = out["Yp"] + vn                                                                  # :537-541
             d_prior = np.zeros((nsteps, B, p.nd))
             if p.nd:                                                 # dhat is carried unchanged between steps (:655-668)
                 d_prior[0] = _bcast(p.dhat0, B, p.nd); d_prior[1:] = out["D_HAT"][:-1]
@@ -73,10 +100,16 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
             ms, _ = s.last_kernel_ms()
             out["TIME_DYN"] = np.full(nsteps, ms * 1e-3 / nsteps); out["TIME_SS"] = np.zeros(nsteps)
         else:
-            out = _stepwise(p, s, x0_p, x0_m, nsteps, sched, warm_start=warm_start)
+            out = _stepwise(p, s, x0_p, x0_m, nsteps, sched, warm_start=warm_start, vn=vn, wn=wn)
+        if vn is not None:
+            out["V_WN"] = vn
+        if wn is not None:
+            out["W_WN"] = wn
     finally:
         if own:
             s.close()
+        elif noise_set:      # (also after an exception: a caller-owned solver does not keep this run's draws)
+            s.loop_set_noise(None, None)
     if gather:
         if total is None:
             if comm is not None and comm.world > 1:
@@ -86,8 +119,9 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
     return out
 
 
-def _stepwise(p, s, x0_p, x0_m, nsteps, sched, warm_start=False):
-    """The reference's call sequence, MPC_code.py:519-816, with each solver call going through the C-ABI."""
+def _stepwise(p, s, x0_p, x0_m, nsteps, sched, warm_start=False, vn=None, wn=None):
+    """The reference's call sequence, MPC_code.py:519-816, with each solver call going through the C-ABI.  ``vn`` / ``wn``: white noise on the measurement
+    and on the plant state after its step, [nsteps, B, ny] / [nsteps, B, nxp] (:537-541, 822-827) - both are the caller's side of the seam."""
     B, n = x0_p.shape[0], p.nx
     x, xhat = x0_p.copy(), x0_m.copy()
     u = _bcast(p.u0, B, p.nu).copy(); dhat = _bcast(p.dhat0, B, p.nd).copy() if p.nd else np.zeros((B, 0))
@@ -110,6 +144,8 @@ def _stepwise(p, s, x0_p, x0_m, nsteps, sched, warm_start=False):
         log["Xp"].append(x.copy()); log["X_HAT"].append(xhat.copy())      # :519-520
         log["Y_HAT"].append(xhat @ p.C.T + p.fy_const + (dhat @ p.Cd.T if p.nd else 0.0) + py0)   # :524
         y = x @ p.Cp.T + sched["pyp"][k] + py0                          # :534
+        if vn is not None:
+            y = y + vn[k]                                               # :537-541
         log["Yp"].append(y.copy())
         if p.estimator != "none":
             xi, Pk = s.kf_update(y, np.hstack([xhat, dhat]), Pk)          # :577-650
@@ -136,4 +172,6 @@ def _stepwise(p, s, x0_p, x0_m, nsteps, sched, warm_start=False):
         log["STATUS_DYN"].append(o["status"]); log["STATUS_SS"].append(t["status"])
         log["ITERS_DYN"].append(o["iters"]); log["ITERS_SS"].append(t["iters"])
         x = p.plant_step(x, u, k * p.h, sched["pxp"][k] + (px0 if p.has_model_params else 0.0))                               # :813-816 (p_xmp = p_x_k, :502-505)
+        if wn is not None:
+            x = x + wn[k]                                               # :822-827
     return {k: np.array(v) for k, v in log.items()}

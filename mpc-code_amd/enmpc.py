@@ -14,6 +14,7 @@ import numpy as np
 
 from . import econcodegen
 from .capi import MpcAmdError
+from .noise import loop_noise  # noqa: F401  (the draws of both white noises; the linear path uses the same function)
 
 ENMPC_EXPORTS = ("enmpc_create", "enmpc_destroy", "enmpc_last_error", "enmpc_build_info", "enmpc_alloc", "enmpc_set_state", "enmpc_run",
                  "enmpc_sync", "enmpc_get_log", "enmpc_last_kernel_ms", "enmpc_set_kernel", "enmpc_get_kernel", "enmpc_time_kernels",
@@ -268,27 +269,6 @@ class EnmpcSolver:
             raise KeyError(name)
         self._chk(self.lib.enmpc_get_log(self.h, name.encode(), out.ctypes.data_as(ct.c_void_p)), "enmpc_get_log")
         return out
-
-
-def loop_noise(problem, nsteps: int, B: int, seed: int):
-    """The draws of the reference's white noises for nsteps x B instances from ``numpy.random.default_rng(seed)``: ``V_WN`` = sqrtm(R_wn) N(0, I) on the measurement
-    (MPC_code.py:537-541) and ``W_WN`` = G_wn sqrtm(Q_wn) N(0, I) on the plant state after its step (:822-827) - None where the example does not define them.  Per step
-    first the measurement's draws, then the state's."""
-    def root(S):
-        ev, evec = np.linalg.eigh(0.5 * (S + S.T))      # the symmetric square root scipy.linalg.sqrtm returns for a covariance
-        return (evec * np.sqrt(np.maximum(ev, 0.0))) @ evec.T
-    p, rng = problem, np.random.default_rng(seed)
-    if getattr(p, "R_wn", None) is None and getattr(p, "G_wn", None) is None:
-        raise ValueError("noise_seed: the example defines neither R_wn nor G_wn / Q_wn")
-    Rv = None if p.R_wn is None else root(p.R_wn)
-    Gw = None if p.G_wn is None else p.G_wn @ root(p.Q_wn)
-    V, W = [], []
-    for _ in range(nsteps):
-        if Rv is not None:
-            V.append(rng.standard_normal((B, p.ny)) @ Rv.T)
-        if Gw is not None:
-            W.append(rng.standard_normal((B, p.nxp)) @ Gw.T)
-    return (np.stack(V) if V else None), (np.stack(W) if W else None)
 
 
 def run_enmpc_stepwise(problem, x0_p, nsteps: Optional[int] = None, device: int = 0, solver: Optional[EnmpcSolver] = None, plant=None, noise_seed: Optional[int] = None):

@@ -144,6 +144,11 @@ class LinearMPCProblem:
     Hu_ss: Optional[np.ndarray] = None
     Hd_ss: Optional[np.ndarray] = None
     h0_ss: Optional[np.ndarray] = None
+    # white noise of the loop (MPC_code.py:537-541, 822-827): covariance of the measurement noise [ny, ny]; input matrix and covariance of the state noise
+    # [nxp, nxp], a pair - driver.run_closed_loop(noise_seed=...) draws them (noise.loop_noise); None: absent
+    R_wn: Optional[np.ndarray] = None
+    G_wn: Optional[np.ndarray] = None
+    Q_wn: Optional[np.ndarray] = None
 
     @property
     def n_user_rows(self) -> int:
@@ -246,7 +251,7 @@ def problem_from_namespace(ns: Dict[str, Any], name: str = "") -> LinearMPCProbl
     for bad in ("User_fxm_Cont", "User_fxm_Dis", "User_fym", "User_fxp_Dis", "User_fyp",
                 "User_fobj_Cont", "User_fobj_Dis", "User_fobj_Coll", "User_fssobj", "User_vfin",
                 "User_h_eq", "r_x", "rss_y",
-                "def_pxmp", "def_pymp", "R_wn", "G_wn"):
+                "def_pxmp", "def_pymp"):
         if _has(ns, bad) and ns[bad] is not None:
             raise UnsupportedProblem(f"'{bad}' is outside the batched linear hot path (later scope row)")
     for flag in ("ssjacid", "StateFeedback", "Fp_nominal", "Adaptation", "Collocation",
@@ -267,6 +272,17 @@ def problem_from_namespace(ns: Dict[str, Any], name: str = "") -> LinearMPCProbl
     nx, nu, ny = ns["x"].size1(), ns["u"].size1(), ns["y"].size1()
     nd, nxp = ns["d"].size1(), ns["xp"].size1()
     N, h, Nsim = int(ns["N"]), float(ns["h"]), int(ns["Nsim"])
+    wn = {k: _has(ns, k) and ns[k] is not None for k in ("R_wn", "G_wn", "Q_wn")}
+    if wn["G_wn"] != wn["Q_wn"]:
+        raise UnsupportedProblem("G_wn and Q_wn (the state noise, MPC_code.py:822-827) have to come together")
+    if wn["R_wn"] or wn["G_wn"]:
+        # the reference's noise is unseeded (a run is not reproducible even there): the batched loops are deterministic and run noise-free unless asked - said out loud
+        import warnings
+        warnings.warn("R_wn / G_wn: the white noise of the example (unseeded in the reference, MPC_code.py:537-541, 822-827) is simulated only on request: the loops run "
+                      "noise-free unless called with noise_seed=...", UserWarning, stacklevel=3)
+    R_wn = _mat(ns["R_wn"], ny, ny, "R_wn") if wn["R_wn"] else None
+    G_wn = _mat(ns["G_wn"], nxp, nxp, "G_wn") if wn["G_wn"] else None
+    Q_wn = _mat(ns["Q_wn"], nxp, nxp, "Q_wn") if wn["Q_wn"] else None
 
     A = _mat(ns["A"], nx, nx, "A")
     B = _mat(ns["B"], nx, nu, "B")
@@ -414,6 +430,7 @@ def problem_from_namespace(ns: Dict[str, Any], name: str = "") -> LinearMPCProbl
         TermCons=bool(ns.get("TermCons", False)), def_px=ns.get("def_px"), def_py=ns.get("def_py"),
         slacks=slacks, Ws=Ws, Gx=Gx, Gu=Gu, Gd=Gd, g0=g0,
         Gx_ss=Gx_ss, Gu_ss=Gu_ss, Gd_ss=Gd_ss, g0_ss=g0_ss, Hx_ss=Hx_ss, Hu_ss=Hu_ss, Hd_ss=Hd_ss, h0_ss=h0_ss,
+        R_wn=R_wn, G_wn=G_wn, Q_wn=Q_wn,
     )
     return prob
 

@@ -7,7 +7,8 @@
 Loads the file unmodified (mpc-code_amd/exfile.py), runs the closed loop of MPC_code.py:485-827 through the HIP path the problem belongs to
 (mpc_code_amd.run_example) and stores the reference's result arrays (U, X_HAT, XS, US, Xp, ... : [nsteps, batch, dim]) in an .npz; prints a
 summary line per array.  `--batch B --spread s`: B instances whose plant and model start states are the file's own times (1 + s U(-1, 1))
-(s = 0: B copies).  `-o NAME=VALUE` overrides a variable of the file (a Python literal), e.g. the horizons of the BASELINE configurations."""
+(s = 0: B copies).  `--noise-seed S`: the file's white noises (R_wn on the measurements, G_wn / Q_wn on the plant state), drawn from
+numpy.random.default_rng(S) - without it the loops run noise-free; the draws are stored as V_WN / W_WN.  `-o NAME=VALUE` overrides a variable of the file (a Python literal), e.g. the horizons of the BASELINE configurations."""
 import argparse
 import ast
 import os
@@ -27,6 +28,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--nsteps", type=int, default=None, help="default: the file's Nsim")
     ap.add_argument("--max-sqp", type=int, default=None, help="non-linear tracking path: SQP iterations per OCP (default 1: real-time iteration)")
+    ap.add_argument("--noise-seed", type=int, default=None, help="simulate the file's white noises R_wn, G_wn / Q_wn with this seed (default: noise-free)")
     ap.add_argument("-o", "--override", action="append", default=[], metavar="NAME=VALUE")
     ap.add_argument("--out", default=None, help="write the result arrays to this .npz")
     ap.add_argument("--load-only", action="store_true", help="load and classify the file, then stop (no GPU needed)")
@@ -45,8 +47,10 @@ def main(argv=None):
     rng = np.random.default_rng(a.seed)
     x0p = np.tile(np.asarray(p.x0_p, dtype=float), (a.batch, 1)) * (1.0 + a.spread * rng.uniform(-1, 1, size=(a.batch, len(p.x0_p))))
     kw = {}
+    if a.noise_seed is not None:      # (every path's loop takes it: driver.run_closed_loop, nmpc.run_nmpc_closed_loop, enmpc.run_enmpc_closed_loop)
+        kw["noise_seed"] = a.noise_seed
     if isinstance(p, m.EconomicMPCProblem):
-        out = m.run_example(p, x0_p=x0p, nsteps=a.nsteps)
+        out = m.run_example(p, x0_p=x0p, nsteps=a.nsteps, **kw)
     else:
         x0m = np.tile(np.asarray(p.x0_m, dtype=float), (a.batch, 1)) * (1.0 + a.spread * rng.uniform(-1, 1, size=(a.batch, len(p.x0_m))))
         if a.max_sqp is not None and isinstance(p, m.NonlinearMPCProblem):
