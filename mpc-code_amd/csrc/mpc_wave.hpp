@@ -61,6 +61,9 @@ struct WvCfg {
     __host__ __device__ static constexpr size_t lds_doubles(int keep_per_inst, int N) { return (size_t)t_doubles(N) + NI * QN + NI * OUT + NI * keep_per_inst; }
 };
 
+template <int V>
+struct WvInt { static constexpr int value = V; };      // a block's place in its group, as a constant (immediate offsets inside asm statements)
+
 template <int NS, int NU, int NC>
 struct WvIter { double sl[NC], sh[NC], ll[NC], lh[NC], u[NU], z[NS]; };      // one block of one instance (lane = block)
 
@@ -423,6 +426,11 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
     // The same products on the same operands as the generic path below: not one rounding differs.
     constexpr bool VF = SB == 1 && !HASM && !kWvGenericTiles;
 #define MPC_MM "v_mfma_f64_4x4x4_4b_f64 "
+    // VF && !LTV: an LDS read issued from inside a statement (operands named dst / addr, offset [off]), and what stands in its place
+    // where a block has nothing to read ahead.  Both count as one wait state.
+#define MPC_WV_RD(dst, addr) "ds_read_b64 %[" #dst "], %[" #addr "] offset:%[off]\n\t"
+#define MPC_WV_NORD(dst, addr) "s_nop 0\n\t"
+    auto wv_lds_addr = [](const double *p) { return (unsigned)(unsigned long long)p; };      // T is LDS: the low half of the flat address is the LDS byte address
     // Everything a pass needs per lane is rebuilt at its start from a lane index the compiler cannot see through: as loop
     // invariants of the iteration loop these registers would stay live across the element-wise phases (and spill there).
     struct TileCtx {
@@ -535,6 +543,104 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             if (LTV) { f[d][NF - 3] = q_a[off]; f[d][NF - 2] = q_b[off]; f[d][NF - 1] = q_bt[off]; }
         };
         MPC_UNROLL for (int d = 0; d < PD; d++) fetch(d, -d);
+        if constexpr (VF && !LTV) {
+            // The statements of the VF path below, with the LDS reads of the next group issued from inside them (see tile_rhs): a block's
+            // sigma_z, sigma_u, s0, s1 and hz are used up by the adds in front of its first statement, which hosts their reads - three in
+            // place of the s_nop 2, one between X1 and Psi, one in the tail - and hu is read behind K' hu in the third.  The second
+            // statement waits for all of them and names their registers.  (NU = 1: s1 is read from the row of zeros.)
+            unsigned a_sz = wv_lds_addr(q_sz[0]) - 64, a_su = wv_lds_addr(q_su) - 64, a_s0 = wv_lds_addr(q_s0) - 64, a_s1 = wv_lds_addr(q_s1) - 64;
+            unsigned a_hu = wv_lds_addr(q_hu) - 64, a_hz = wv_lds_addr(q_hz[0]) - 64;
+            const double Br0 = c.Br[0], Btr0 = c.Btr[0], Ar0 = c.Ar[0][0], BE00 = BE0[0], BE10 = BE1[0], Qr0 = Qr[0][0];
+            double Pm0 = Pm[0][0], PC0 = 0.0;
+            auto step = [&](auto D, auto MORE) {
+                constexpr int d = decltype(D)::value, dp = (d + PD - 1) % PD;
+                constexpr bool more = decltype(MORE)::value;
+                Pm0 += f[d][0];
+                const double X0i = RE0 + f[d][2], X1i = RE1 + f[d][3], PV0 = f[d][5] + PC0, Rs = Rr + f[d][1];
+                double PB, BtP, PA, psv, X0, X1, Psi;
+                // PB = P B, BtP = B'P, PA = P A, psv = hu + B'(hz + p+);  then X0 / X1 (rows of Lambda) and Psi = B'PA.  PB is read 6 wait
+                // states after it issued (BtP, PA, psv, three reads), PA 7 (psv, three reads, X0, X1, read);  the tail is 6 wait states.
+#define MPC_FAC_STMT1(RD) \
+                "s_nop 1\n\t" \
+                MPC_MM "%[pb], %[pm], %[br], 0\n\t" \
+                MPC_MM "%[btp], %[br], %[pm], 0\n\t" \
+                MPC_MM "%[pa], %[pm], %[ar], 0\n\t" \
+                MPC_MM "%[psv], %[br], %[pv], %[hu]\n\t" \
+                RD(sz, asz) RD(su, asu) RD(s0, as0) \
+                MPC_MM "%[x0], %[be0], %[pb], %[x0i]\n\t" \
+                MPC_MM "%[x1], %[be1], %[pb], %[x1i]\n\t" \
+                RD(s1, as1) \
+                MPC_MM "%[psi], %[br], %[pa], 0\n\t" \
+                RD(hz, ahz) \
+                "s_nop 4" \
+                : [pb] "=&v"(PB), [btp] "=&v"(BtP), [pa] "=&v"(PA), [psv] "=&v"(psv), [x0] "=&v"(X0), [x1] "=&v"(X1), [psi] "=&v"(Psi), \
+                  [sz] "+v"(f[d][0]), [su] "+v"(f[d][1]), [s0] "+v"(f[d][2]), [s1] "+v"(f[d][3]), [hz] "+v"(f[d][5]) \
+                : [pm] "v"(Pm0), [br] "v"(Br0), [ar] "v"(Ar0), [pv] "v"(PV0), [hu] "v"(f[d][4]), [be0] "v"(BE00), [be1] "v"(BE10), [x0i] "v"(X0i), [x1i] "v"(X1i), \
+                  [asz] "v"(a_sz), [asu] "v"(a_su), [as0] "v"(a_s0), [as1] "v"(a_s1), [ahz] "v"(a_hz), [off] "i"((PD - d) * 8) : "memory"
+                if constexpr (more) asm volatile(MPC_FAC_STMT1(MPC_WV_RD));
+                else asm volatile(MPC_FAC_STMT1(MPC_WV_NORD));
+#undef MPC_FAC_STMT1
+                const double a = dpp_move<0x00, 0xF>(X0, X0);
+                double adjm, adjk, det;
+                if (NU == 1) { det = a; adjm = c_1; adjk = k_1; pd_min = dmin(pd_min, a); }
+                else {
+                    const double off = dpp_move<0x55, 0xF>(X0, X0), dd = dpp_move<0x55, 0xF>(X1, X1);
+                    det = __builtin_fma(a, dd, -(off * off));
+                    adjk = __builtin_fma(k_d, dd, __builtin_fma(k_a, a, k_o * off));
+                    adjm = __builtin_fma(c_d, dd, __builtin_fma(c_a, a, c_o * off));
+                    pd_min = dmin(pd_min, dmin(a, det));
+                }
+                // K = (-adj Psi) / det, the reciprocal's Newton steps behind the product (see the VF path below).  The statement opens with
+                // the wait for the reads of the first statement and of the block before (hu), two wait states like the s_nop 1 it replaces.
+                double Kk0;
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 0\n\t" MPC_MM "%[kk], %[adjk], %[psi], 0"
+                             : [kk] "=v"(Kk0), "+v"(det), "+v"(f[d][0]), "+v"(f[d][1]), "+v"(f[d][2]), "+v"(f[d][3]), "+v"(f[d][5]), "+v"(f[dp][4])
+                             : [adjk] "v"(adjk), [psi] "v"(Psi) : "memory");
+                const double rdet = frcp(det);
+                asm("s_nop 1" : "+v"(Kk0) : "v"(rdet));
+                Kk0 *= rdet;
+                const double mL = adjm * rdet, mLi = adjk * rdet;
+                // R~ K, Acl = A + B K, Tm = P Acl = PA + PB K, K' hu, kff = -Lambda^-1 psv;  then K' R~ K + Q, Acl' Tm, p = Acl'(hz + p+) + K' hu.
+                // R~ K is read 7 wait states after it issued (Acl, Tm, K' hu, read, kff, s_nop 1), Acl 7, Tm 6, K' hu (as srcC) 6; kff goes to
+                // LDS 11 wait states after it issued.
+                double RK0, Acl0, Tm0, a2, KFF, acc, acc2, PCn;
+#define MPC_FAC_STMT3(RD) \
+                "s_nop 1\n\t" \
+                MPC_MM "%[rk], %[rs], %[kk], 0\n\t" \
+                MPC_MM "%[acl], %[btr], %[kk], %[ar]\n\t" \
+                MPC_MM "%[tm], %[btp], %[kk], %[pa]\n\t" \
+                MPC_MM "%[a2], %[kk], %[hu], 0\n\t" \
+                RD(hu, ahu) \
+                MPC_MM "%[kff], %[mli], %[psv], 0\n\t" \
+                "s_nop 1\n\t" \
+                MPC_MM "%[acc], %[kk], %[rk], %[q]\n\t" \
+                MPC_MM "%[acc2], %[acl], %[tm], 0\n\t" \
+                MPC_MM "%[pcn], %[acl], %[pv], %[a2]\n\t" \
+                "s_nop 5" \
+                : [rk] "=&v"(RK0), [acl] "=&v"(Acl0), [tm] "=&v"(Tm0), [a2] "=&v"(a2), [kff] "=&v"(KFF), [acc] "=&v"(acc), [acc2] "=&v"(acc2), [pcn] "=&v"(PCn), [hu] "+v"(f[d][4]) \
+                : [rs] "v"(Rs), [kk] "v"(Kk0), [btr] "v"(Btr0), [ar] "v"(Ar0), [btp] "v"(BtP), [pa] "v"(PA), [mli] "v"(mLi), [psv] "v"(psv), [q] "v"(Qr0), [pv] "v"(PV0), \
+                  [ahu] "v"(a_hu), [off] "i"((PD - d) * 8) : "memory"
+                if constexpr (more) asm volatile(MPC_FAC_STMT3(MPC_WV_RD));
+                else asm volatile(MPC_FAC_STMT3(MPC_WV_NORD));
+#undef MPC_FAC_STMT3
+                q_st[0][-d] = sel_k0 ? Kk0 : (st_l ? mL : KFF);
+                if (NS >= 4) q_sf[-d] = KFF;
+                Pm0 = acc + acc2;      // symmetric up to rounding; the recursion does not amplify the difference
+                PC0 = PCn;
+            };
+            const int G = N / PD, rem = N - G * PD;
+            for (int g = 0; g < G; g++) {
+                step(WvInt<0>{}, WvInt<1>{}); step(WvInt<1>{}, WvInt<1>{}); step(WvInt<2>{}, WvInt<1>{}); step(WvInt<3>{}, WvInt<1>{});
+                a_sz -= PD * 8; a_su -= PD * 8; a_s0 -= PD * 8; a_s1 -= PD * 8; a_hu -= PD * 8; a_hz -= PD * 8;
+                q_st[0] -= stp[0]; q_sf -= stpf;
+            }
+            if (0 < rem) step(WvInt<0>{}, WvInt<0>{});
+            if (1 < rem) step(WvInt<1>{}, WvInt<0>{});
+            if (2 < rem) step(WvInt<2>{}, WvInt<0>{});
+            // the reads in flight (hu of the last block) land before the registers go back to the compiler
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0][4]), "+v"(f[1][4]), "+v"(f[2][4]), "+v"(f[3][4]));
+            return;
+        }
         auto block = [&](int d, bool more) {
             double sz[SB], HZ[SB];
             MPC_UNROLL for (int i = 0; i < SB; i++) { sz[i] = f[d][i]; HZ[i] = f[d][SB + 4 + i]; }
@@ -696,6 +802,77 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             if (LTV) { f[d][NF - 3] = q_a[off]; f[d][NF - 2] = q_b[off]; f[d][NF - 1] = q_bt[off]; }
         };
         MPC_UNROLL for (int d = 0; d < PD; d++) fetch(d, -d);
+        if constexpr (VF && !LTV) {
+            // Skewed by one block.  Of a block's six products only Acl' p+ and psv -> kff hang on p+; Acl, K' hu and Acl' hz + K' hu are
+            // known a block ahead.  A dependent product holds the pipe 32 cycles and an independent one issued behind it costs 12
+            // (profiles/calib_mfma_f64_fill.txt), so block d's statement runs Acl' p+ and psv, then in their shadow the three products
+            // of block d + 1, with kff once psv is 6 wait states old.  The LDS reads of the next group are issued from the statement,
+            // each behind the last product that reads the register it lands in; the compiler does not see them, so every statement closes
+            // with the wait for the reads of the one before it and names their registers: lgkmcnt(4) leaves its own four reads in flight
+            // (LDS operations return in order), lgkmcnt(0) in the blocks left over, which read nothing.  Addresses are LDS byte addresses
+            // set back by 64: the immediate offsets of the backward reads stay positive.
+            unsigned a_hu = wv_lds_addr(q_hu) - 64, a_li = wv_lds_addr(q_li) - 64, a_hz = wv_lds_addr(q_hz[0]) - 64, a_k = wv_lds_addr(q_k[0]) - 64;
+            const double Br0 = c.Br[0], Btr0 = c.Btr[0], Ar0 = c.Ar[0][0];
+            double PC0 = 0.0, Acl0, cstc;
+            {
+                // block 0's Acl, K' hu, Acl' hz + K' hu: Acl is read 6 wait states after it issued (K' hu, s_nop 4), K' hu (as srcC) 5
+                double cst0;
+                asm volatile("s_nop 1\n\t"
+                             MPC_MM "%0, %3, %4, %5\n\t"
+                             MPC_MM "%1, %4, %6, 0\n\t"
+                             "s_nop 4\n\t"
+                             MPC_MM "%2, %0, %7, %1\n\t"
+                             "s_nop 1"
+                             : "=&v"(Acl0), "=&v"(cst0), "=&v"(cstc) : "v"(Btr0), "v"(f[0][3]), "v"(Ar0), "v"(f[0][0]), "v"(f[0][2]));
+            }
+            // Wait states, counted from the issue of the producer:  kff reads psv 6 (read, Acl, read, K' hu, read, s_nop 0);  Acl' hz + K' hu
+            // reads Acl 6 (read, K' hu, read, s_nop 0, kff, read) and K' hu (srcC) 4;  Acl' p+ of the next statement reads Acl 9 or more;
+            // kff goes to LDS 9 after it issued (read, one product, s_waitcnt, s_nop 5);  p+ = (Acl' hz + K' hu) + Acl' p+ behind the statement
+            // reads Acl' p+ 17 after it issued.  Without the reads (the blocks left over) an s_nop 0 stands in for each.
+#define MPC_RHS_STMT(RD, W) \
+            "s_nop 1\n\t" \
+            MPC_MM "%[dyn], %[acl], %[pc], 0\n\t" \
+            MPC_MM "%[psv], %[br], %[pv], %[hu]\n\t" \
+            RD(hu, ahu) \
+            MPC_MM "%[acln], %[btr], %[k1], %[ar]\n\t" \
+            RD(hz, ahz) \
+            MPC_MM "%[cst0n], %[k1], %[hu1], 0\n\t" \
+            RD(k, ak) \
+            "s_nop 0\n\t" \
+            MPC_MM "%[kff], %[li], %[psv], 0\n\t" \
+            RD(li, ali) \
+            MPC_MM "%[cstn], %[acln], %[hz1], %[cst0n]\n\t" \
+            "s_waitcnt lgkmcnt(" W ")\n\t" \
+            "s_nop 5" \
+            : [dyn] "=&v"(dyn), [psv] "=&v"(psv), [acln] "=&v"(AclN), [cst0n] "=&v"(cst0N), [kff] "=&v"(KFF), [cstn] "=&v"(cstN), \
+              [hu] "+v"(f[d][0]), [li] "+v"(f[d][1]), [hz] "+v"(f[d][2]), [k] "+v"(f[d][3]), "+v"(f[dp][0]), "+v"(f[dp][1]), "+v"(f[dp][2]), "+v"(f[dp][3]) \
+            : [acl] "v"(Acl0), [pc] "v"(PC0), [pv] "v"(PV0), [br] "v"(Br0), [btr] "v"(Btr0), [ar] "v"(Ar0), [hu1] "v"(f[dn][0]), [hz1] "v"(f[dn][2]), [k1] "v"(f[dn][3]), \
+              [ahu] "v"(a_hu), [ali] "v"(a_li), [ahz] "v"(a_hz), [ak] "v"(a_k), [off] "i"((PD - d) * 8) : "memory"
+            auto step = [&](auto D, auto MORE) {
+                constexpr int d = decltype(D)::value, dn = (d + 1) % PD, dp = (d + PD - 1) % PD;
+                const double PV0 = f[d][2] + PC0;
+                double dyn, psv, AclN, cst0N, KFF, cstN;
+                if constexpr (decltype(MORE)::value) asm volatile(MPC_RHS_STMT(MPC_WV_RD, "4"));
+                else asm volatile(MPC_RHS_STMT(MPC_WV_NORD, "0"));
+                q_st[-d] = KFF;
+                PC0 = cstc + dyn;
+                cstc = cstN; Acl0 = AclN;
+            };
+#undef MPC_RHS_STMT
+            const int G = N / PD, rem = N - G * PD;
+            for (int g = 0; g < G; g++) {
+                step(WvInt<0>{}, WvInt<1>{}); step(WvInt<1>{}, WvInt<1>{}); step(WvInt<2>{}, WvInt<1>{}); step(WvInt<3>{}, WvInt<1>{});
+                a_hu -= PD * 8; a_li -= PD * 8; a_hz -= PD * 8; a_k -= PD * 8; q_st -= stp;
+            }
+            if (0 < rem) step(WvInt<0>{}, WvInt<0>{});
+            if (1 < rem) step(WvInt<1>{}, WvInt<0>{});
+            if (2 < rem) step(WvInt<2>{}, WvInt<0>{});
+            // the reads in flight land before the registers go back to the compiler
+            asm volatile("s_waitcnt lgkmcnt(0)"
+                         : "+v"(f[0][0]), "+v"(f[0][1]), "+v"(f[0][2]), "+v"(f[0][3]), "+v"(f[1][0]), "+v"(f[1][1]), "+v"(f[1][2]), "+v"(f[1][3]),
+                           "+v"(f[2][0]), "+v"(f[2][1]), "+v"(f[2][2]), "+v"(f[2][3]), "+v"(f[3][0]), "+v"(f[3][1]), "+v"(f[3][2]), "+v"(f[3][3]), "+v"(Acl0), "+v"(cstc));
+            return;
+        }
         auto block = [&](int d, bool more) {
             const double HU = f[d][0], mLi = f[d][1];
             double HZ[SB], Kk[SB];
@@ -776,6 +953,62 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             if (LTV) { f[d][NF - 2] = q_at[off]; f[d][NF - 1] = q_bt[off]; }
         };
         MPC_UNROLL for (int d = 0; d < PD; d++) fetch(d, d);
+        if constexpr (VF && !LTV) {
+            // Skewed by one block (see tile_rhs): block d's statement runs the chain product dz+ = Acl dz + B kff and du = K dz + kff, and in
+            // their shadow Acl' and B kff of block d + 1.  The reads of the next group's K, K', kff follow the last product that reads
+            // this group's (d: du;  K of d: Acl' in the statement before).
+            unsigned a_kf = wv_lds_addr(q_kf), a_k = wv_lds_addr(q_k[0]), a_kt = wv_lds_addr(q_kt[0]);
+            const double Btr0 = c.Btr[0], Atr0 = c.Atr[0][0];
+            double DZ0 = 0.0, Aclt, a0;
+            asm volatile("s_nop 1\n\t"
+                         MPC_MM "%0, %2, %3, %4\n\t"
+                         MPC_MM "%1, %3, %5, 0\n\t"
+                         "s_nop 2"
+                         : "=&v"(Aclt), "=&v"(a0) : "v"(f[0][1]), "v"(Btr0), "v"(Atr0), "v"(f[0][0]));
+            // Wait states, counted from the issue of the producer:  dz+ reads Acl' 6 (B kff, s_waitcnt, s_nop 1, s_nop 1, and a product
+            // needs 6 as srcA), B kff (srcC) 5, the dz+ before it 9 or more;  the selects behind the statement read du 7 (two reads, two
+            // products, s_waitcnt, s_nop 1) and dz+ 9.  Without the reads (the blocks left over) an s_nop 0 stands in for each.
+            // The wait closes the statement and leaves the statement's own three reads in flight (lgkmcnt(3); LDS operations return in
+            // order): what it waits for - the reads of the statement before, whose registers it names, and the store of the block
+            // before - was issued four products ago, so nothing stalls in front of dz+.  The blocks left over read nothing: lgkmcnt(0).
+#define MPC_FWD_STMT(RD, W) \
+            "s_nop 1\n\t" \
+            MPC_MM "%[dzn], %[aclt], %[dz], %[a0]\n\t" \
+            RD(k, ak) \
+            MPC_MM "%[du], %[kt], %[dz], %[kf]\n\t" \
+            RD(kf, akf) \
+            RD(kt, akt) \
+            MPC_MM "%[acltn], %[k1], %[btr], %[atr]\n\t" \
+            MPC_MM "%[a0n], %[btr], %[kf1], 0\n\t" \
+            "s_waitcnt lgkmcnt(" W ")\n\t" \
+            "s_nop 1" \
+            : [dzn] "=&v"(DZn), [du] "=&v"(DUv), [acltn] "=&v"(AcltN), [a0n] "=&v"(a0N), [kf] "+v"(f[d][0]), [k] "+v"(f[d][1]), [kt] "+v"(f[d][2]), \
+              "+v"(f[dp][0]), "+v"(f[dp][1]), "+v"(f[dp][2]) \
+            : [aclt] "v"(Aclt), [a0] "v"(a0), [dz] "v"(DZ0), [kf1] "v"(f[dn][0]), [k1] "v"(f[dn][1]), [btr] "v"(Btr0), [atr] "v"(Atr0), \
+              [akf] "v"(a_kf), [ak] "v"(a_k), [akt] "v"(a_kt), [off] "i"((PD + d) * 8) : "memory"
+            auto step = [&](auto D, auto MORE) {
+                constexpr int d = decltype(D)::value, dn = (d + 1) % PD, dp = (d + PD - 1) % PD;
+                double DZn, DUv, AcltN, a0N;
+                if constexpr (decltype(MORE)::value) asm volatile(MPC_FWD_STMT(MPC_WV_RD, "3"));
+                else asm volatile(MPC_FWD_STMT(MPC_WV_NORD, "0"));
+                q_st[0][d] = st_u ? DUv : DZn;
+                DZ0 = DZn; Aclt = AcltN; a0 = a0N;
+            };
+#undef MPC_FWD_STMT
+            const int G = N / PD, rem = N - G * PD;
+            for (int g = 0; g < G; g++) {
+                step(WvInt<0>{}, WvInt<1>{}); step(WvInt<1>{}, WvInt<1>{}); step(WvInt<2>{}, WvInt<1>{}); step(WvInt<3>{}, WvInt<1>{});
+                a_kf += PD * 8; a_k += PD * 8; a_kt += PD * 8; q_st[0] += stp[0];
+            }
+            if (0 < rem) step(WvInt<0>{}, WvInt<0>{});
+            if (1 < rem) step(WvInt<1>{}, WvInt<0>{});
+            if (2 < rem) step(WvInt<2>{}, WvInt<0>{});
+            // the reads in flight land before the registers go back to the compiler; the last products are 6 wait states old before a VALU may overwrite them
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 5"
+                         : "+v"(f[0][0]), "+v"(f[0][1]), "+v"(f[0][2]), "+v"(f[1][0]), "+v"(f[1][1]), "+v"(f[1][2]), "+v"(f[2][0]), "+v"(f[2][1]), "+v"(f[2][2]),
+                           "+v"(f[3][0]), "+v"(f[3][1]), "+v"(f[3][2]), "+v"(Aclt), "+v"(a0));
+            return;
+        }
         auto block = [&](int d, bool more) {
             const double KFF = f[d][0];
             double Kk[SB], KkT[SB];
@@ -936,6 +1169,8 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
     }
 }
 #undef MPC_MM
+#undef MPC_WV_RD
+#undef MPC_WV_NORD
 
 
 // ------------------------------------------------------------------------------------------------------------------------

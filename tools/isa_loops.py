@@ -5,7 +5,8 @@
 
 A loop is what lies between a backward branch and its target (the blocks from the target label to the branching one, summed in the
 manner of tools/isa_blocks.py); nested loops are reported each on its own.  Every instruction is one of VALU / MFMA / accvgpr / LDS /
-nop / wait / scratch / other.  Also printed: the kernel's register counts and private segment, and the totals of the whole kernel.
+nop / wait / scratch / other; mfma_adjacent counts the matrix-core products whose next instruction is another product (no
+instruction issued in the gap between them).  Also printed: the kernel's register counts and private segment, and the totals of the whole kernel.
 The self-looping blocks that hold v_mfma_f64 are the tile sweeps of mpc_wave.hpp (tile_factor, tile_forward twice, tile_rhs)."""
 import collections
 import json
@@ -42,17 +43,23 @@ def kernel_lines(lines, pat):
 def parse_blocks(body):
     """[(label, Counter of kinds, [branch targets])] in program order; inline-asm text counts like any other line"""
     blocks = [["entry", collections.Counter(), []]]
+    prev = None
     for l in body:
         t = l.split(";")[0].strip()
         m = re.match(r"^(\.LBB\d+_\d+):", t)
         if m:
             blocks.append([m.group(1), collections.Counter(), []])
+            prev = None
             continue
         if not t or t.startswith((".", "//")) or t.endswith(":"):
             continue
         op = t.split()[0]
-        blocks[-1][1][classify(op)] += 1
+        kind = classify(op)
+        blocks[-1][1][kind] += 1
         blocks[-1][1]["instrs"] += 1
+        if kind == "mfma" and prev == "mfma":
+            blocks[-1][1]["mfma_adjacent"] += 1
+        prev = kind
         if op.startswith(("s_cbranch", "s_branch")):
             blocks[-1][2].append(t.split()[-1])
     return blocks
@@ -68,7 +75,7 @@ def loops_of(blocks):
                 for b in blocks[index[tgt]:i + 1]:
                     tot.update(b[1])
                 out.append({"head": tgt, "tail": label, "blocks": i + 1 - index[tgt], "self_loop": tgt == label,
-                            **{k: tot[k] for k in ("instrs",) + KINDS}})
+                            **{k: tot[k] for k in ("instrs",) + KINDS + ("mfma_adjacent",)}})
     return out
 
 
