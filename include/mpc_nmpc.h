@@ -63,6 +63,12 @@ int nmpc_set_schedule(nmpc_handle *h, int32_t nsteps, const double *ysp /* [nste
 /* white noise on the measurements of the resident loop: v [nsteps][B][ny] is added to y_k before the estimator - the reference's sqrtm(R_wn) N(0, I) of
  * MPC_code.py:537-541 (unseeded there; the draws are the caller's here: nmpc.py makes them from a seed).  NULL: none.  After nmpc_alloc */
 int nmpc_set_noise(nmpc_handle *h, int32_t nsteps, const double *v);
+/* white noise on the plant state of the resident loop: w [nsteps][B][nxp] is added after the plant's step, x_p <- (Fx_p(x_p, u) + pxp_k) + w_k - the reference's
+ * G_wn sqrtm(Q_wn) N(0, I) of MPC_code.py:822-827 (unseeded there; the draws are the caller's: no generator of random numbers runs on the device).  The log Xp[k]
+ * is the state that was measured: it includes w_{k-1}.  NULL: none.  Valid after nmpc_alloc, which clears it; nmpc_set_state does not touch it; the call drains the
+ * stream first.  -1: nsteps outside 1..max_steps, and nmpc_run over steps the noise does not cover; a refused call leaves what was in force.  The per-call seam has
+ * no counterpart: the plant between the calls is the caller's side, who adds w to what nmpc_plant_step returns - the same two additions, to the bit */
+int nmpc_set_state_noise(nmpc_handle *h, int32_t nsteps, const double *w /* [nsteps][B][nxp] or NULL */);
 /* steps [k0, k0+nsteps); asynchronous.  max_sqp SQP iterations per OCP (1 = real-time iteration), stopped early when the
  * trajectory moves less than sqp_tol */
 int nmpc_run(nmpc_handle *h, int32_t k0, int32_t nsteps, int32_t max_sqp, double sqp_tol);

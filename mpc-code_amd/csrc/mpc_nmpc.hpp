@@ -16,7 +16,27 @@
 #pragma once
 #include "mpc_device.hpp"
 
+#include <type_traits>
+
 namespace mpc {
+
+// offree = 'lin' with a CONTINUOUS model (Utilities.py:157-183): the step is RK4 of f, then + Bd d - NlModel::LIN_BD and the table NlModel::BD when the
+// generated header declares them (a discrete 'lin' model has its + Bd d inside the traced map), nothing otherwise
+template <class T, class = void> struct LinBdOf { static constexpr bool value = false; };
+template <class T> struct LinBdOf<T, std::void_t<decltype(T::LIN_BD)>> { static constexpr bool value = T::LIN_BD; };
+
+// xn += Bd d after the integration (entries that are literal zeros fold away)
+template <class M>
+__device__ __forceinline__ void lin_bd_add(const double *d, double *xn)
+{
+    if constexpr (LinBdOf<M>::value) {
+        MPC_UNROLL for (int i = 0; i < M::NX; i++) {
+            double s = 0.0;
+            MPC_UNROLL for (int j = 0; j < M::ND; j++) { if (M::BD[i][j] != 0.0) s += M::BD[i][j] * d[j]; }
+            xn[i] += s;
+        }
+    } else { (void)d; (void)xn; }
+}
 
 // x(t + h): MX RK4 steps of dx/dt = f(x, u, d, t)
 // Each integrator comes twice: *_inl (always inlined: the wave-autonomous kernel parks its iterates in the accumulation registers,
@@ -42,6 +62,7 @@ __device__ __forceinline__ void rk4_model_inl(const double *x0, const double *u,
         MPC_UNROLL for (int i = 0; i < NX; i++) x[i] += dt / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
     }
     MPC_UNROLL for (int i = 0; i < NX; i++) xn[i] = x[i];
+    lin_bd_add<M>(d, xn);
 }
 
 template <class M>
@@ -76,12 +97,15 @@ __device__ __noinline__ void rk4_plant(const double *x0, const double *u, double
 // The same with forward sensitivities: S = d x(t+h) / d [x0 | u | d], propagated through every Runge-Kutta stage
 // (dK_i = f_x(X_i) dX_i + [0 | f_u | f_d](X_i)).  Out: xn, A = S[:, :NX], B = S[:, NX:NX+NU], G = S[:, NX+NU:].
 // WITHG = false: the sensitivities with respect to the disturbance are not propagated (G is left untouched): target and OCP
-// linearise in (x, u) only.
+// linearise in (x, u) only.  LIN_BD: f does not depend on d (the loader checks it), so those columns are not propagated at all and
+// G = Bd; xn carries the + Bd d.
 template <class M, bool WITHG = true>
 __device__ __forceinline__ void rk4_model_sens_inl(const double *x0, const double *u, const double *d, double t, double h,
                                                    double *xn, double (*A)[M::NX], double (*B)[M::NU], double (*G)[M::ND > 0 ? M::ND : 1])
 {
-    constexpr int NX = M::NX, NU = M::NU, ND = M::ND, NDD = ND > 0 ? ND : 1, NP = NX + NU + (WITHG ? ND : 0);
+    constexpr int NX = M::NX, NU = M::NU, ND = M::ND, NDD = ND > 0 ? ND : 1;
+    constexpr bool PROPG = WITHG && !LinBdOf<M>::value;      // the d columns go through the integration
+    constexpr int NP = NX + NU + (PROPG ? ND : 0);
     if (M::DISCRETE) { M::f_jac(x0, u, d, t, xn, A, B, G); return; }
     const double dt = h / M::MX;
     double x[NX], S[NX][NP];
@@ -114,7 +138,11 @@ __device__ __forceinline__ void rk4_model_sens_inl(const double *x0, const doubl
         xn[i] = x[i];
         MPC_UNROLL for (int j = 0; j < NX; j++) A[i][j] = S[i][j];
         MPC_UNROLL for (int j = 0; j < NU; j++) B[i][j] = S[i][NX + j];
-        if (WITHG) { MPC_UNROLL for (int j = 0; j < ND; j++) G[i][j] = S[i][NX + NU + (WITHG ? j : 0)]; }
+        if (PROPG) { MPC_UNROLL for (int j = 0; j < ND; j++) G[i][j] = S[i][NX + NU + (PROPG ? j : 0)]; }
+    }
+    if constexpr (LinBdOf<M>::value) {
+        if (WITHG) { MPC_UNROLL for (int i = 0; i < NX; i++) { MPC_UNROLL for (int j = 0; j < ND; j++) G[i][j] = M::BD[i][j]; } }
+        lin_bd_add<M>(d, xn);
     }
 }
 

@@ -10,7 +10,9 @@ Covered: continuous-time model and plant (``User_fxm_Cont``, ``User_fym``, ``Use
 entering the model non-linearly (``offree = "nl"``: the estimate ``dhat`` is an argument of the model, ``Utilities.py:126-129``),
 quadratic stage cost on ``x - xs`` and ``u - us`` (``Q``, ``R``; no terminal cost: ``defVfin`` returns 0 without ``A``,
 ``Utilities.py:398-399``), quadratic target cost (``Qss``, ``Rss``), bounds on u, x, y (outputs that are single states),
-saturation of ``dhat``, extended Kalman filter (``Estimator.py:313-386``), user inequality rows ``User_g_ineq(x, u, y, d, t, px, py) <= 0`` at every
+saturation of ``dhat``, the linear disturbance model on a continuous model (``offree = "lin"``: RK4 of ``f``, then ``+ Bd d``, ``Utilities.py:157-183``; ``+ Cd d`` on the
+output, ``:237-238``), ``StateFeedback`` (``Fy_model = x (+ Cd d)``, ``Fy_p = x_p``, ``:201-205, 84-86``), the white noises ``R_wn`` and ``G_wn / Q_wn`` (kept for the
+loops of :mod:`nmpc`), extended Kalman filter (``Estimator.py:313-386``), user inequality rows ``User_g_ineq(x, u, y, d, t, px, py) <= 0`` at every
 stage of the horizon (``Control_Calc.py:94-100,132-147``; carried as stage states).  Anything else raises ``UnsupportedProblem``.
 """
 from __future__ import annotations
@@ -70,11 +72,14 @@ class NonlinearMPCProblem:
     max_iter: int = 100
     defSP: Optional[Callable] = None
     R_wn: Optional[np.ndarray] = None      # covariance of the white noise the reference adds to every measurement (MPC_code.py:538-541): run_nmpc_stepwise(noise_seed=...)
+    G_wn: Optional[np.ndarray] = None      # input matrix [nxp, nw] and covariance [nw, nw] of the white noise on the plant state after its step (MPC_code.py:822-827)
+    Q_wn: Optional[np.ndarray] = None
+    StateFeedback: bool = False            # hy = x (+ Cd d), hp = xp: built by the loader, User_fym / User_fyp are not read
     name: str = ""
     ycols: List[int] = None         # output row i is state ycols[i] (bounded outputs are boxes on states)
     discrete: bool = False          # f is the discrete map Fx (User_fxm_Dis, Utilities.py:186-198), not a right-hand side to integrate
     plant_discrete: bool = False
-    offree: str = "nl"              # "nl": d is an argument of the model; "lin": + Bd d, + Cd d (folded into f / hy)
+    offree: str = "nl"              # "nl": d is an argument of the model; "lin": + Bd d, + Cd d (folded into f / hy; continuous model: + Bd d after the integration, not in f)
     Bd: Optional[np.ndarray] = None
     Cd: Optional[np.ndarray] = None
     estimator: str = "ekf"          # "ekf" | "lue" (fixed gain K)
@@ -149,6 +154,20 @@ class NonlinearMPCProblem:
             xp = xp + dt / 6.0 * (k1 + 2 * k2 + 2 * k3 + k4)
         return xp
 
+    def model_step(self, x, u, d, t):
+        """Fx_model(x, u, d, t): ``Mx`` RK4 steps of the model over ``h`` (Utilities.py:157-183), + Bd d after them with offree = 'lin'; the user's map (with its
+        + Bd d folded in) for a discrete model (:186-198)."""
+        x = np.array(x, dtype=np.float64); dt = self.h / self.Mx
+        dd = d if self.nd else None
+        f = lambda x_, t_: self._stack(st.evaluate(self.f, self._vals(x=x_, u=u, d=dd, t=t_)), x_.shape[:-1])
+        if self.discrete:
+            return f(x, t)
+        for s in range(self.Mx):
+            ts = t + s * dt
+            k1 = f(x, ts); k2 = f(x + 0.5 * dt * k1, ts + 0.5 * dt); k3 = f(x + 0.5 * dt * k2, ts + 0.5 * dt); k4 = f(x + dt * k3, ts + dt)
+            x = x + dt / 6.0 * (k1 + 2 * k2 + 2 * k3 + k4)
+        return x + np.asarray(d, dtype=np.float64) @ self.Bd.T if self.offree == "lin" else x
+
     def plant_output(self, xp, u, t):
         return self._stack(st.evaluate(self.hp, self._vals(xp=xp, u=u, t=t)), np.shape(xp)[:-1])
 
@@ -168,16 +187,19 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
     """Classify a non-linear Ex-file namespace (reference MPC_code.py:84-257 probes) and trace its functions."""
     has = lambda k: k in ns and ns[k] is not None and not k.startswith("__")
     for bad in ("User_fobj_Cont", "User_fobj_Dis", "User_fobj_Coll", "User_fssobj",
-                "User_h_eq", "User_g_ineq_SS", "User_h_eq_SS", "r_x", "rss_y", "def_px", "def_py", "def_pxmp", "def_pymp", "A", "G_wn"):
+                "User_h_eq", "User_g_ineq_SS", "User_h_eq_SS", "r_x", "rss_y", "def_px", "def_py", "def_pxmp", "def_pymp", "A"):
         if has(bad):
             raise UnsupportedProblem(f"'{bad}' is outside the non-linear path built so far")
-    if has("R_wn"):
+    if has("G_wn") != has("Q_wn"):
+        raise UnsupportedProblem("G_wn and Q_wn (the state noise, MPC_code.py:822-827) have to come together")
+    if has("R_wn") or has("G_wn"):
         # the reference adds UNSEEDED Gaussian noise to every measurement (MPC_code.py:538-541): a run is not reproducible even there.
         # The batched loops are deterministic and run noise-free unless asked otherwise - said out loud, not silently (Ex_NMPC.py ships R_wn): with noise_seed = s
-        # nmpc.run_nmpc_closed_loop (draws on the device, nmpc_set_noise) and nmpc.run_nmpc_stepwise (the measurement is the caller's) add seeded noise of this covariance
+        # nmpc.run_nmpc_closed_loop (draws on the device, nmpc_set_noise / nmpc_set_state_noise) and nmpc.run_nmpc_stepwise (measurement and plant are the caller's) add
+        # seeded noise of these covariances: R_wn on the measurement, G_wn sqrtm(Q_wn) N(0, I) on the plant state after its step (:822-827)
         import warnings
-        warnings.warn("R_wn: the measurement noise of the example (unseeded in the reference, MPC_code.py:538-541) is simulated only on request: the loops run noise-free unless called with noise_seed=...", UserWarning, stacklevel=3)
-    for flag in ("ssjacid", "StateFeedback", "Fp_nominal", "Adaptation", "Collocation", "slacks", "TermCons", "mhe", "ContForm",
+        warnings.warn("R_wn / G_wn: the white noise of the example (unseeded in the reference, MPC_code.py:537-541, 822-827) is simulated only on request: the loops run noise-free unless called with noise_seed=...", UserWarning, stacklevel=3)
+    for flag in ("ssjacid", "Fp_nominal", "Adaptation", "Collocation", "slacks", "TermCons", "mhe", "ContForm",
                  "DUFormEcon", "kal", "kalss", "estimating"):
         if ns.get(flag, False) is True:
             raise UnsupportedProblem(f"flag {flag}=True is outside the non-linear path built so far")
@@ -187,15 +209,20 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
         raise UnsupportedProblem("dmin and dmax have to come together (the estimate is clipped to both, MPC_code.py:657-664)")
     discrete = has("User_fxm_Dis")
     plant_discrete = has("User_fxp_Dis")
-    for req in ("User_fxm_Dis" if discrete else "User_fxm_Cont", "User_fym", "User_fxp_Dis" if plant_discrete else "User_fxp_Cont", "User_fyp",
+    sfb = ns.get("StateFeedback", False) is True      # Fy_model = x (+ Cd d), Fy_p = x_p: the output maps are the loader's (Utilities.py:201-205, 84-86)
+    for req in ("User_fxm_Dis" if discrete else "User_fxm_Cont", "User_fxp_Dis" if plant_discrete else "User_fxp_Cont") + (() if sfb else ("User_fym", "User_fyp")) + (
                 "Q", "Qss", "N", "h", "Nsim", "x", "u", "y", "d", "xp"):
         if not has(req):
             raise UnsupportedProblem(f"'{req}' missing: not a non-linear example with a quadratic cost")
     offree = ns.get("offree", "no")
+    if sfb and offree == "no":
+        raise UnsupportedProblem("StateFeedback = True with offree = 'no' (another estimator branch, MPC_code.py:579) is outside the non-linear path built so far: it needs a disturbance model")
     if offree not in ("nl", "lin"):
         raise UnsupportedProblem("the non-linear path needs a disturbance model (offree = 'nl' or 'lin')")
-    if offree == "lin" and not discrete:
-        raise UnsupportedProblem("offree = 'lin' with a continuous-time model is outside the non-linear path built so far")
+    if offree == "lin":
+        for req in ("Bd", "Cd"):
+            if not has(req):
+                raise UnsupportedProblem(f"'{req}' missing: offree = 'lin' needs Bd and Cd")
     if ns.get("ekf", False):
         est = "ekf"
         for req in ("Q_kf", "R_kf"):
@@ -208,20 +235,30 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
     else:
         raise UnsupportedProblem("the non-linear path needs ekf = True or lue = True")
     nx, nu, ny, nd, nxp = ns["x"].size1(), ns["u"].size1(), ns["y"].size1(), ns["d"].size1(), ns["xp"].size1()
+    if sfb:
+        if ny != nx or nxp != nx:
+            raise UnsupportedProblem(f"StateFeedback = True needs ny = nx and nxp = nx (the output is the state): nx = {nx}, ny = {ny}, nxp = {nxp}")
+        if has("def_pyp"):
+            raise UnsupportedProblem("StateFeedback = True with def_pyp: the reference's Fy_p = x_p drops pyp (Utilities.py:84-86); leave def_pyp out")
     vx, vu, vd, vxp, vt = st.symvec("x", nx), st.symvec("u", nu), st.symvec("d", nd), st.symvec("xp", nxp), st.Sym.var("t")
     col = st.SymMat.col
     zero = lambda n: st.SymMat.zeros(n)
     f = _trace(ns["User_fxm_Dis" if discrete else "User_fxm_Cont"], (col(vx), col(vu), col(vd), vt, zero(nx)))     # Utilities.py:160,188
-    hy = _trace(ns["User_fym"], (col(vx), col(vu), col(vd), vt, zero(ny)))                # Utilities.py:229
+    hy = list(vx) if sfb else _trace(ns["User_fym"], (col(vx), col(vu), col(vd), vt, zero(ny)))                # Utilities.py:229; StateFeedback: :201-205
     fp = _trace(ns["User_fxp_Dis" if plant_discrete else "User_fxp_Cont"], (col(vxp), vt, col(vu), zero(nxp), zero(nxp)))  # Utilities.py:61,85
-    hp = _trace(ns["User_fyp"], (col(vxp), col(vu), vt, zero(ny), zero(ny)))         # Utilities.py:94
+    hp = list(vxp) if sfb else _trace(ns["User_fyp"], (col(vxp), col(vu), vt, zero(ny), zero(ny)))         # Utilities.py:94; StateFeedback: :84-86
     if len(f) != nx or len(hy) != ny or len(fp) != nxp or len(hp) != ny:
         raise UnsupportedProblem("a user function returns a vector of the wrong length")
     hy_user = list(hy)      # the user's map alone: with offree = 'lin' the + Cd d below is carried per instance by the kernels' output rows
     Bd = Cd = None
     if offree == "lin":        # Fx_model = F(x,u,d,t) + Bd d, Fy_model = h(x,u,d,t) + Cd d (Utilities.py:189-193,231-233)
         Bd, Cd = _mat(ns["Bd"], nx, nd, "Bd"), _mat(ns["Cd"], ny, nd, "Cd")
-        f = [f[i] + sum((float(Bd[i, j]) * vd[j] for j in range(nd)), st.Sym.const(0.0)) for i in range(nx)]
+        if discrete:
+            f = [f[i] + sum((float(Bd[i, j]) * vd[j] for j in range(nd)), st.Sym.const(0.0)) for i in range(nx)]
+        # a continuous model: d is not an input of the integrated function unless offree = 'nl' (Utilities.py:127-130,167), and + Bd d comes AFTER the
+        # integration (:181-183) - it stays out of f; the generated model adds it to the step (nlcodegen: LIN_BD, BD)
+        elif any(not e.is_const(0.0) for row in st.jacobian(f, vd) for e in row):
+            raise UnsupportedProblem("User_fxm_Cont depends on d with offree = 'lin': the disturbance enters the model through Bd and Cd only (offree = 'nl' takes d as an argument)")
         hy = [hy[i] + sum((float(Cd[i, j]) * vd[j] for j in range(nd)), st.Sym.const(0.0)) for i in range(ny)]
     if any(not e.is_const(0.0) for row in st.jacobian(hy, vu) for e in row):
         raise UnsupportedProblem("User_fym depends on u: the target and the OCP linearise the output map in x only")
@@ -283,6 +320,10 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
         Pf = np.array([[e.val for e in row] for row in Hs], dtype=np.float64)
         Pf = 0.5 * (Pf + Pf.T)
     P0 = np.array(ns["P0"], dtype=np.float64) if has("P0") else np.zeros((nx + nd, nx + nd))
+    G_wn = Q_wn = None
+    if has("G_wn"):      # G_wn [nxp, nw], Q_wn [nw, nw]: the number of noise components is G_wn's second dimension (MPC_code.py:822-827)
+        nwn = int(np.atleast_2d(np.asarray(ns["G_wn"], dtype=np.float64)).shape[1])
+        G_wn, Q_wn = _mat(ns["G_wn"], nxp, nwn, "G_wn"), _mat(ns["Q_wn"], nwn, nwn, "Q_wn")
     return NonlinearMPCProblem(
         nx=nx, nu=nu, ny=ny, nd=nd, nxp=nxp, N=int(ns["N"]), h=float(ns["h"]), Nsim=int(ns["Nsim"]), Mx=int(ns.get("Mx", 10)),
         f=f, hy=hy, fp=fp, hp=hp, Q=_mat(ns["Q"], nx, nx, "Q"), R=R, Qss=_mat(ns["Qss"], ny, ny, "Qss"), Rss=Rss,
@@ -294,10 +335,11 @@ def nl_problem_from_namespace(ns: Dict[str, Any], name: str = "") -> NonlinearMP
         Q_kf=_mat(ns["Q_kf"], nx + nd, nx + nd, "Q_kf") if est == "ekf" else None, R_kf=_mat(ns["R_kf"], ny, ny, "R_kf") if est == "ekf" else None, P0=P0,
         x0_p=_vec(ns["x0_p"], nxp, 0.0), x0_m=_vec(ns["x0_m"], nx, 0.0), u0=_vec(ns["u0"], nu, 0.0),
         dhat0=_vec(ns.get("dhat0"), nd, 0.0) if has("dhat0") else np.zeros(nd),
-        max_iter=int(ns.get("Sol_itmax", 100)), defSP=ns.get("defSP"), R_wn=(_mat(ns["R_wn"], ny, ny, "R_wn") if has("R_wn") else None), name=name or str(ns.get("__name__", "")), ycols=ycols,
+        max_iter=int(ns.get("Sol_itmax", 100)), defSP=ns.get("defSP"), R_wn=(_mat(ns["R_wn"], ny, ny, "R_wn") if has("R_wn") else None),
+        G_wn=G_wn, Q_wn=Q_wn, StateFeedback=sfb, name=name or str(ns.get("__name__", "")), ycols=ycols,
         funcs={k: ns[k] for k in ("User_fxm_Cont", "User_fxm_Dis", "User_fym", "User_fxp_Cont", "User_fxp_Dis", "User_fyp", "User_g_ineq") if has(k)}, g_ineq=g_ineq,
         discrete=discrete, plant_discrete=plant_discrete, offree=offree, Bd=Bd, Cd=Cd, estimator=est,
         K=_mat(ns["K"], nx + nd, ny, "K") if est == "lue" else None, DUForm=DUForm, DUssForm=DUssForm,
         Dumin=_vec(ns.get("Dumin"), nu, -INF) if du_bounded else None, Dumax=_vec(ns.get("Dumax"), nu, INF) if du_bounded else None, Pf=Pf,
-        def_pxp=ns.get("def_pxp"), def_pyp=ns.get("def_pyp"),
+        def_pxp=ns.get("def_pxp"), def_pyp=None if sfb else ns.get("def_pyp"),
     )

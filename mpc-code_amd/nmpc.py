@@ -13,11 +13,12 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import nlcodegen
+from . import noise as _noise
 from .capi import MpcAmdError
 
 NMPC_EXPORTS = ("nmpc_create", "nmpc_destroy", "nmpc_last_error", "nmpc_build_info", "nmpc_alloc", "nmpc_set_state", "nmpc_set_schedule",
                 "nmpc_run", "nmpc_sync", "nmpc_get_log", "nmpc_last_kernel_ms", "nmpc_set_kernel", "nmpc_set_groups", "nmpc_get_kernel", "nmpc_time_kernels",
-                "nmpc_wave_kernel_ms", "nmpc_ekf_update", "nmpc_target_solve", "nmpc_ocp_solve", "nmpc_plant_step", "nmpc_set_noise")
+                "nmpc_wave_kernel_ms", "nmpc_ekf_update", "nmpc_target_solve", "nmpc_ocp_solve", "nmpc_plant_step", "nmpc_set_noise", "nmpc_set_state_noise")
 
 _dp = ct.POINTER(ct.c_double)
 _ip = ct.POINTER(ct.c_int32)
@@ -46,6 +47,7 @@ def load_nmpc_library(path: str) -> ct.CDLL:
     lib.nmpc_set_state.argtypes = [vp] + [_dp] * 7
     lib.nmpc_set_schedule.argtypes = [vp, ct.c_int32, _dp, _dp, _dp, _dp]
     lib.nmpc_set_noise.argtypes = [vp, ct.c_int32, _dp]
+    lib.nmpc_set_state_noise.argtypes = [vp, ct.c_int32, _dp]
     lib.nmpc_run.argtypes = [vp, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_double]
     lib.nmpc_sync.argtypes = [vp]
     lib.nmpc_set_kernel.argtypes = [vp, ct.c_int32]
@@ -142,15 +144,17 @@ class NmpcSolver:
                                              None if pxp is None else pxp.ctypes.data_as(_dp), None if pyp is None else pyp.ctypes.data_as(_dp)), "nmpc_set_schedule")
         self.steps = ysp.shape[0]
 
-    def set_noise(self, v: Optional[np.ndarray]):
-        """white noise on the measurements of the resident loop, v [nsteps, B, ny] (MPC_code.py:537-541), or None"""
-        if v is None:
-            self._chk(self.lib.nmpc_set_noise(self.h, 0, None), "nmpc_set_noise")
-            return
-        v = _c(np.asarray(v, dtype=np.float64))
-        if v.ndim != 3 or v.shape[1:] != (self.B, self.p.ny):
-            raise ValueError(f"noise: [nsteps, {self.B}, {self.p.ny}] expected, got {v.shape}")
-        self._chk(self.lib.nmpc_set_noise(self.h, v.shape[0], v.ctypes.data_as(_dp)), "nmpc_set_noise")
+    def set_noise(self, v: Optional[np.ndarray], w: Optional[np.ndarray] = None):
+        """white noise of the resident loop: v [nsteps, B, ny] on the measurements (MPC_code.py:537-541) and w [nsteps, B, nxp] on the plant state after its step
+        (:822-827); None switches the one off"""
+        for a, d, fn, what in ((v, self.p.ny, self.lib.nmpc_set_noise, "nmpc_set_noise"), (w, self.p.nxp, self.lib.nmpc_set_state_noise, "nmpc_set_state_noise")):
+            if a is None:
+                self._chk(fn(self.h, 0, None), what)
+                continue
+            a = _c(np.asarray(a, dtype=np.float64))
+            if a.ndim != 3 or a.shape[1:] != (self.B, d):
+                raise ValueError(f"noise: [nsteps, {self.B}, {d}] expected, got {a.shape}")
+            self._chk(fn(self.h, a.shape[0], a.ctypes.data_as(_dp)), what)
 
     # ---- per-call seam: the reference's three solver calls of a step (include/mpc_nmpc.h) --------------------------------------------------
     def ekf_update(self, y, u_prev, xhat, dhat, P):
@@ -244,13 +248,24 @@ def measurement_noise(problem, nsteps: int, B: int, seed: int) -> np.ndarray:
     return np.stack([rng.standard_normal((B, problem.ny)) @ Rv.T for _ in range(nsteps)])
 
 
+def path_noise(problem, nsteps: int, B: int, seed: int):
+    """``(V_WN, W_WN)`` of a seed on THIS path, None where the example does not define the matrices.  NOT :func:`noise.loop_noise` under another name: a file
+    with ``G_wn / Q_wn`` gets that function's draws (per step first the measurement's, then the state's, as on the linear and the economic path), but a file
+    without them keeps :func:`measurement_noise`'s - all measurement draws of a step in one block - so that ``V_WN`` of a seed stays what it was before this path
+    carried a state noise."""
+    if getattr(problem, "G_wn", None) is not None:
+        return _noise.loop_noise(problem, nsteps, B, seed)
+    return measurement_noise(problem, nsteps, B, seed), None
+
+
 def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None, solver: Optional[NmpcSolver] = None, max_sqp: int = 1, sqp_tol: float = 1e-9,
                       device: int = 0, plant=None, noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
     """The reference's loop body call by call (MPC_code.py:485-827): per step the measurement (the Ex-file's plant output on the host), ``ekf_update``
     (defEstimator), ``target_solve`` (solver_ss), ``ocp_solve`` (solver) and the plant - ``plant(x_p [B, nxp], u [B, nu], t) -> x_p+`` of the caller, or the
     device's.  With the device's plant: :func:`run_nmpc_closed_loop` on the instance-per-lane kernel to the bit (when the plant output is exact on the host).
     ``noise_seed``: the white noise of the example's ``R_wn`` on every measurement, ``y_k += sqrtm(R_wn) N(0, I)`` (MPC_code.py:538-541; unseeded there), one draw per
-    step and instance from ``numpy.random.default_rng(noise_seed)``; the draws come back as ``V_WN`` [nsteps, B, ny]."""
+    step and instance from ``numpy.random.default_rng(noise_seed)``; the draws come back as ``V_WN`` [nsteps, B, ny].  With ``G_wn / Q_wn`` also the state noise,
+    ``x_p <- (Fx_p + pxp_k) + G_wn sqrtm(Q_wn) N(0, I)`` (:822-827), added here on the caller's side of the seam and returned as ``W_WN`` [nsteps, B, nxp]."""
     p = problem
     nsteps = p.Nsim if nsteps is None else int(nsteps)
     x_p = (p.x0_p[None] if x0_p is None else np.atleast_2d(np.asarray(x0_p, dtype=np.float64))).copy()
@@ -268,7 +283,7 @@ def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = Non
         u, xs, us = _rows(p.u0, B, p.nu).copy(), xhat.copy(), _rows(p.u0, B, p.nu).copy()
         keys = ("U", "X_HAT", "XS", "US", "Xp", "D_HAT", "STATUS_DYN", "STATUS_SS", "ITERS_DYN", "SQP_DYN", "SQP_SS")
         out = {k: [] for k in keys}
-        vn = measurement_noise(p, nsteps, B, noise_seed) if noise_seed is not None else None
+        vn, wn = path_noise(p, nsteps, B, noise_seed) if noise_seed is not None else (None, None)
         for k in range(nsteps):
             t = k * p.h
             out["Xp"].append(x_p.copy()); out["X_HAT"].append(xhat.copy())
@@ -279,11 +294,15 @@ def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = Non
             xs, us, st_s, sq_s = s.target_solve(dhat, sch["ysp"][k], sch["usp"][k], xs, us)
             u, xhat, st_d, it_d, sq_d = s.ocp_solve(xhat, dhat, xs, us, u, max_sqp, sqp_tol)
             x_p = s.plant_step(u, x_p, sch["pxp"][k]) if plant is None else np.asarray(plant(x_p, u, t), dtype=np.float64) + sch["pxp"][k]
+            if wn is not None:                                               # :822-827
+                x_p = x_p + wn[k]
             for kk, v in (("U", u), ("XS", xs), ("US", us), ("D_HAT", dhat[:, :p.nd]), ("STATUS_DYN", st_d), ("STATUS_SS", st_s), ("ITERS_DYN", it_d), ("SQP_DYN", sq_d), ("SQP_SS", sq_s)):
                 out[kk].append(np.array(v))
         res = {k: np.stack(v) for k, v in out.items() if not (k == "D_HAT" and p.nd == 0)}
         if vn is not None:
             res["V_WN"] = vn
+        if wn is not None:
+            res["W_WN"] = wn
         return res
     finally:
         if own:
@@ -292,7 +311,8 @@ def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = Non
 
 def run_nmpc_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None, solver: Optional[NmpcSolver] = None,
                          max_sqp: int = 1, sqp_tol: float = 1e-9, device: int = 0, noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
-    """``noise_seed``: white noise of the example's ``R_wn`` on every measurement (:func:`measurement_noise`; returned as ``V_WN``); None: the deterministic loop.
+    """``noise_seed``: white noise of the example's ``R_wn`` on every measurement and of its ``G_wn / Q_wn`` on the plant state after its step (:func:`path_noise`;
+    returned as ``V_WN`` / ``W_WN``; on the device: ``nmpc_set_noise``, ``nmpc_set_state_noise``); None: the deterministic loop.
     ``max_sqp = 1``: one real-time iteration per step (one linearisation along the shifted previous trajectory, one QP);
     larger: iterate each OCP to the NLP's KKT point, what the reference's IPOPT call returns (``MPC_code.py:775-783``).
     Result arrays carry the reference's names (``MPC_code.py:877-895``), shaped [nsteps, B, dim]."""
@@ -307,14 +327,16 @@ def run_nmpc_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = 
         s.alloc(B, nsteps)
         s.set_state(x0_p, x0_m)
         s.set_schedule(p.schedules(nsteps))
-        vn = measurement_noise(p, nsteps, B, noise_seed) if noise_seed is not None else None
-        if vn is not None:      # (a caller-owned solver keeps the noise its caller installed)
-            s.set_noise(vn)
+        vn, wn = path_noise(p, nsteps, B, noise_seed) if noise_seed is not None else (None, None)
+        if noise_seed is not None:      # (a caller-owned solver keeps the noise its caller installed)
+            s.set_noise(vn, wn)
         s.run(0, nsteps, max_sqp, sqp_tol)
         s.sync()
         out = {k: s.get_log(k) for k in list(s.LOGS) + list(s.ILOGS) if not (k == "D_HAT" and p.nd == 0)}
         if vn is not None:
             out["V_WN"] = vn
+        if wn is not None:
+            out["W_WN"] = wn
         ms = s.last_kernel_ms()
         out["TIME_DYN"] = np.full(nsteps, ms * 1e-3 / nsteps); out["TIME_SS"] = np.zeros(nsteps)
         u_prev = np.concatenate([_rows(p.u0, B, p.nu)[None], out["U"][:-1]]) if nsteps else out["U"]

@@ -22,5 +22,5 @@ def loop_noise(problem, nsteps: int, B: int, seed: int):
         if Rv is not None:
             V.append(rng.standard_normal((B, p.ny)) @ Rv.T)
         if Gw is not None:
-            W.append(rng.standard_normal((B, p.nxp)) @ Gw.T)
+            W.append(rng.standard_normal((B, Gw.shape[1])) @ Gw.T)      # (one draw per noise component: nxp of them where G_wn is square)
     return (np.stack(V) if V else None), (np.stack(W) if W else None)
