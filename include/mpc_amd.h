@@ -151,7 +151,8 @@ int mpc_kf_update(mpc_handle *h, int32_t B, const double *y, double *xi_inout, d
 
 /*
  * The closed loop MPC_code.py:485-827 for B instances that share the problem and the schedules and differ
- * in their state.  Step order: measure (:524-534) -> estimate (:577-650) -> target (:693-718) -> OCP
+ * in their state, in the white noise added per step (mpc_loop_set_noise) and - optionally - in their set points
+ * (mpc_loop_set_setpoints: every instance tracks a schedule of its own).  Step order: measure (:524-534) -> estimate (:577-650) -> target (:693-718) -> OCP
  * (:733-805) -> plant (:813-816).  State lives in HBM inside the handle between calls.
  *
  *   mpc_loop_set_state   upload [B][.] arrays: x_p [nxp], xhat [nx], dhat [nd], P [(nx+nd)^2] (NULL unless
@@ -188,13 +189,22 @@ int mpc_loop_set_model_schedule(mpc_handle *h, int32_t nsteps, const double *px,
  * the handle's stream before it overwrites a buffer.  Returns -1 for nsteps outside 1..max_steps, -8 for v on a handle with MPC_EST_NONE (nothing reads
  * the measurement) - either leaves the noise that was in force untouched; mpc_loop_run over steps beyond the noise's nsteps returns -1. */
 int mpc_loop_set_noise(mpc_handle *h, int32_t nsteps, const double *v, const double *w);
+/* Set points per step and per instance (defSP(t), MPC_code.py:677-680, evaluated by the caller for every instance): ysp [nsteps][B][ny] or NULL, usp [nsteps][B][nu]
+ * or NULL.  A NULL array leaves that quantity on the shared schedule of mpc_loop_set_schedule; both NULL: off.  Step k of the arrays is step k of the schedule (the k0 of
+ * mpc_loop_run).  The target problem of instance b at step k is solved with ysp[k][b] / usp[k][b] where mpc_target_solve's par_ss has ysp / usp (:693); nothing else reads a
+ * set point.  The shared schedule is still required: it carries pxp, pyp and the step count.  Valid after mpc_loop_alloc, which clears the arrays; mpc_loop_set_state does
+ * not touch them; a later mpc_loop_set_schedule clears them (the last statement of the set points wins: a stale per-instance array never overrides a new schedule).  The
+ * call drains the handle's stream before it overwrites a buffer.  Returns -1 for nsteps outside 1..max_steps, which leaves what was in force untouched; mpc_loop_run over
+ * steps beyond the arrays' nsteps returns -1.  Every loop kernel carries them; a run without them keeps every bit of its results. */
+int mpc_loop_set_setpoints(mpc_handle *h, int32_t nsteps, const double *ysp /* [nsteps][B][ny] or NULL */, const double *usp /* [nsteps][B][nu] or NULL */);
 int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps);
 int mpc_loop_sync(mpc_handle *h);
 int mpc_loop_get_log(mpc_handle *h, const char *name, void *out);
 
 /* Convenience wrapper with host buffers only (set_state, set_schedule, run, sync, get_state):
  * the fused equivalent of calling the three solvers nsteps times from MPC_code.py's loop.  It runs with whatever noise is in force
- * (mpc_loop_set_noise; none after the mpc_loop_alloc it makes itself when the batch, the steps or the log level do not fit). */
+ * (mpc_loop_set_noise; none after the mpc_loop_alloc it makes itself when the batch, the steps or the log level do not fit), and on the
+ * shared schedule it is given: its mpc_loop_set_schedule clears per-instance set points (mpc_loop_set_setpoints). */
 int mpc_closed_loop(mpc_handle *h, int32_t B, int32_t nsteps, double *x_p, double *xhat, double *dhat,
                     double *P, double *u, double *xs, double *us, const double *ysp, const double *usp,
                     const double *xsp, const double *pxp, const double *pyp, double *U_log /* [nsteps][B][nu] or NULL */);

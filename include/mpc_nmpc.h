@@ -69,6 +69,12 @@ int nmpc_set_noise(nmpc_handle *h, int32_t nsteps, const double *v);
  * stream first.  -1: nsteps outside 1..max_steps, and nmpc_run over steps the noise does not cover; a refused call leaves what was in force.  The per-call seam has
  * no counterpart: the plant between the calls is the caller's side, who adds w to what nmpc_plant_step returns - the same two additions, to the bit */
 int nmpc_set_state_noise(nmpc_handle *h, int32_t nsteps, const double *w /* [nsteps][B][nxp] or NULL */);
+/* set points per step and per instance (defSP(t) of every instance, MPC_code.py:677-680), as mpc_loop_set_setpoints of mpc_amd.h: the target problem of instance b at
+ * step k is solved with ysp[k][b] / usp[k][b].  A NULL array leaves that quantity on the shared schedule of nmpc_set_schedule (still required: it carries pxp, pyp and the
+ * step count); both NULL: off.  Step k of the arrays is step k of the schedule.  Valid after nmpc_alloc, which clears them; nmpc_set_state does not touch them; a later
+ * nmpc_set_schedule clears them (the last statement of the set points wins).  The call drains the stream first.  -1: nsteps outside 1..max_steps, which leaves what was in
+ * force untouched, and nmpc_run over steps the arrays do not cover.  Kernels 1, 3 and 4 carry them; a run without them keeps every bit of its results */
+int nmpc_set_setpoints(nmpc_handle *h, int32_t nsteps, const double *ysp /* [nsteps][B][ny] or NULL */, const double *usp /* [nsteps][B][nu] or NULL */);
 /* steps [k0, k0+nsteps); asynchronous.  max_sqp SQP iterations per OCP (1 = real-time iteration), stopped early when the
  * trajectory moves less than sqp_tol */
 int nmpc_run(nmpc_handle *h, int32_t k0, int32_t nsteps, int32_t max_sqp, double sqp_tol);
@@ -99,13 +105,15 @@ int nmpc_wave_kernel_ms(nmpc_handle *h, float *total_ms, int32_t *launches);
  * handle keeps between the calls what the reference's driver keeps - the last optimum, i.e. the shifted guess of :764 - and what this solver's warm
  * start compares against (estimate and targets before their updates).  nmpc_alloc + nmpc_set_state first; then per step, in this order,
  * nmpc_ekf_update, nmpc_target_solve, nmpc_ocp_solve: with nmpc_plant_step in between they reproduce nmpc_run (kernel 1) bit for bit
- * (tests/test_nmpc.py). */
+ * (tests/test_nmpc.py) - with nmpc_target_solve_inst in nmpc_target_solve's place also a run with per-instance set points (nmpc_set_setpoints). */
 /* y [B][ny] this step's measurement, u_prev [B][nu] the input applied over the step before; xhat [B][nx], dhat [B][nd], P [B][(nx+nd)^2]: the
  * estimator's state, prior in / posterior out (P is not used by the fixed-gain observer); dhat is saturated by dmin / dmax when given */
 int nmpc_ekf_update(nmpc_handle *h, const double *y, const double *u_prev, double *xhat, double *dhat, double *P);
 /* ysp [ny], usp [nu]: this step's set points; xs [B][nx], us [B][nu]: the targets of the step before in (first guess of the SQP and us_prev of the
  * input-move cost), this step's out - unchanged when status is 2 (MPC_code.py:714-718); sqp: SQP iterations taken */
 int nmpc_target_solve(nmpc_handle *h, const double *dhat, const double *ysp, const double *usp, double *xs, double *us, int32_t *status, int32_t *sqp);
+/* the same with this step's set points of every instance: ysp [B][ny], usp [B][nu] */
+int nmpc_target_solve_inst(nmpc_handle *h, const double *dhat, const double *ysp, const double *usp, double *xs, double *us, int32_t *status, int32_t *sqp);
 /* u_out [B][nu] the optimal first input, xnext_out [B][nx] the optimiser's next state (MPC_code.py:798-799); the held input and the model's
  * propagation with status 2 (:804-805); iters: interior-point iterations of the last QP */
 int nmpc_ocp_solve(nmpc_handle *h, const double *xhat, const double *dhat, const double *xs, const double *us, const double *u_prev, int32_t max_sqp, double sqp_tol,

@@ -50,6 +50,9 @@ def run_example(problem_or_path, x0_p=None, x0_m=None, nsteps=None, overrides=No
     p = load_problem(problem_or_path, overrides) if isinstance(problem_or_path, (str, bytes, _os.PathLike)) else problem_or_path
     if isinstance(p, EconomicMPCProblem):
         from .enmpc import run_enmpc_closed_loop
+        if kw.get("setpoints") is not None:
+            raise ValueError("setpoints=: the economic path has no set points (defSP is refused there); per-instance set points are carried by the linear and the non-linear tracking path")
+        kw.pop("setpoints", None)
         if x0_m is not None:
             raise ValueError("the economic path starts the model state from the file's x0_m / x_bar (MPC_code.py:449-463); pass x0_p only")
         return run_enmpc_closed_loop(p, p.x0_p[None] if x0_p is None else x0_p, nsteps, **kw)

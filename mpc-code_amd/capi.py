@@ -182,6 +182,7 @@ def load_library(path: Optional[str] = None) -> ct.CDLL:
     lib.mpc_loop_set_schedule.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 5
     lib.mpc_loop_set_model_schedule.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 2
     lib.mpc_loop_set_noise.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 2
+    lib.mpc_loop_set_setpoints.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 2
     lib.mpc_ocp_solve.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 7 + [_dp, _dp, _dp, _ip, _ip, _dp]
     lib.mpc_target_solve.argtypes = [ct.c_void_p, ct.c_int32] + [_dp] * 5 + [_dp, _dp, _dp, _ip, _ip]
     lib.mpc_kf_update.argtypes = [ct.c_void_p, ct.c_int32, _dp, _dp, _dp]
@@ -204,11 +205,37 @@ def load_library(path: Optional[str] = None) -> ct.CDLL:
 
 
 EXPORTS = ("mpc_lin_create", "mpc_destroy", "mpc_last_error", "mpc_ocp_solve", "mpc_get_slacks", "mpc_target_solve", "mpc_kf_update", "mpc_set_model_offsets",
-           "mpc_loop_alloc", "mpc_loop_set_state", "mpc_loop_get_state", "mpc_loop_set_schedule", "mpc_loop_set_model_schedule", "mpc_loop_set_noise", "mpc_loop_run",
+           "mpc_loop_alloc", "mpc_loop_set_state", "mpc_loop_get_state", "mpc_loop_set_schedule", "mpc_loop_set_model_schedule", "mpc_loop_set_noise", "mpc_loop_set_setpoints", "mpc_loop_run",
            "mpc_loop_sync", "mpc_loop_get_log", "mpc_closed_loop", "mpc_last_kernel_ms", "mpc_stream", "mpc_dev_ptr",
            "mpc_pack_u", "mpc_pack_log", "mpc_set_option", "mpc_get_option", "mpc_build_info",
            "mpc_comm_unique_id", "mpc_comm_init", "mpc_comm_destroy", "mpc_comm_rank", "mpc_comm_allgather",
            "mpc_comm_allreduce_max", "mpc_comm_barrier", "mpc_allgather_u", "mpc_allgather_log")
+
+
+def check_setpoints(setpoints, nsteps: int, B: int, ny: int, nu: int):
+    """``setpoints=`` of the closed-loop drivers: a dict with ``ysp`` [nsteps, B, ny] and / or ``usp`` [nsteps, B, nu], every instance's own schedule for the ``B`` rows the
+    call runs.  Returns ``(ysp, usp)`` as contiguous float64 arrays (None where not given); anything else in the dict, or another shape, is a ValueError."""
+    if setpoints is None:
+        return None, None
+    if not isinstance(setpoints, dict) or not setpoints or set(setpoints) - {"ysp", "usp"}:
+        raise ValueError("setpoints: a dict with 'ysp' [nsteps, B, ny] and / or 'usp' [nsteps, B, nu]" + (f", got the keys {sorted(setpoints)}" if isinstance(setpoints, dict) else ""))
+    out = []
+    for k, d in (("ysp", ny), ("usp", nu)):
+        a = setpoints.get(k)
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (int(nsteps), int(B), d):
+                raise ValueError(f"setpoints['{k}']: [{int(nsteps)}, {int(B)}, {d}] expected, got {a.shape}")
+        out.append(a)
+    if out[0] is None and out[1] is None:
+        raise ValueError("setpoints: neither 'ysp' nor 'usp' given")
+    return out[0], out[1]
+
+
+def tracked_setpoints(sched, ysp, usp, nsteps: int, B: int):
+    """``YSP`` / ``USP`` [nsteps, B, .] of a result: what every instance tracked - its own array, or the shared schedule broadcast."""
+    return {"YSP": ysp if ysp is not None else np.repeat(np.asarray(sched["ysp"], dtype=np.float64)[:nsteps, None, :], B, axis=1),
+            "USP": usp if usp is not None else np.repeat(np.asarray(sched["usp"], dtype=np.float64)[:nsteps, None, :], B, axis=1)}
 
 
 def _c(a, shape=None):
@@ -504,6 +531,18 @@ class Solver:
         if any(a is not None and a.shape[0] != n for a in arrs):
             raise ValueError("noise: v and w cover the same number of steps")
         self._chk(self.lib.mpc_loop_set_noise(self.h, int(n), _p(arrs[0]), _p(arrs[1])), "mpc_loop_set_noise")
+
+    def loop_set_setpoints(self, ysp=None, usp=None):
+        """set points per step and per instance: ``ysp`` [nsteps, B, ny], ``usp`` [nsteps, B, nu] (``defSP(t)`` of every instance, ``MPC_code.py:677-680``), step k of
+        the arrays being step k of the schedule; ``None`` leaves that quantity on the shared schedule, both ``None``: off.  A later ``loop_set_schedule`` clears them."""
+        arrs = [None if a is None else _c(a) for a in (ysp, usp)]
+        for a, d in zip(arrs, (self.p.ny, self.p.nu)):
+            if a is not None and (a.ndim != 3 or a.shape[1:] != (self._loop_B, d)):
+                raise ValueError(f"set points: [nsteps, {self._loop_B}, {d}] expected, got {a.shape}")
+        n = next((a.shape[0] for a in arrs if a is not None), 0)
+        if any(a is not None and a.shape[0] != n for a in arrs):
+            raise ValueError("set points: ysp and usp cover the same number of steps")
+        self._chk(self.lib.mpc_loop_set_setpoints(self.h, int(n), _p(arrs[0]), _p(arrs[1])), "mpc_loop_set_setpoints")
 
     def loop_run(self, k0: int, nsteps: int):
         self._chk(self.lib.mpc_loop_run(self.h, int(k0), int(nsteps)), "mpc_loop_run")

@@ -473,6 +473,8 @@ __global__ __launch_bounds__(64 * NW) void loop_kernel_tp(const DevProblem *__re
             double usp[NU], ysp[NY], xs_n[NX], us_n[NU], ys_n[NY];
             MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
             MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
+            if (a.usp_b) { MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = (a.usp_b + (size_t)((size_t)k * NU + i) * Bs)[bq]; }      // this instance's own set points (mpc_loop_set_setpoints)
+            if (a.ysp_b) { MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = (a.ysp_b + (size_t)((size_t)k * NY + i) * Bs)[bq]; }
             int it_ss;
             const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, twk, 1, sh.keepflag + lane);
             if (st_ss != kInfeasible) {
@@ -613,7 +615,8 @@ struct WvKernelCfg {
 // The body of the two entries below.  NOISE: the white noise a.vn / a.wn of mpc_loop_set_noise is read.  A compile-time switch, and a second entry, because the
 // noise-free loop is the benchmark's and its kernel sits at the register limit: a wave-uniform null test on the two pointers inside the one kernel fitted (256 VGPRs,
 // no scratch) but cost the noise-free headline 0.9 % on an MI355X, this form nothing (profiles/lin_noise_cost.txt).  The price is the build: every instantiation of
-// the wave kernel compiles twice.
+// the wave kernel compiles twice.  The same switch carries the other per-instance step inputs, the set points a.ysp_b / a.usp_b of
+// mpc_loop_set_setpoints, each behind its own null test inside that second entry only: no third instantiation.
 template <bool NOISE, int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS, int NHS>
 __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, const LoopArgs &a)
 {
@@ -689,7 +692,19 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
             MPC_UNROLL for (int i = 0; i < ND; i++) dh[i] = kq[KC::K_DH + i];
             MPC_UNROLL for (int i = 0; i < NU; i++) usv[i] = kq[KC::K_US + i];
             int it_ss; double vrow;
-            const int st_ss = target_row16<NX, NU, NY, ND, NGS, NHS>(P, r16, tab, a.usp + k * NU, a.ysp + k * NY, dh, usv, kq + KC::K_TW, twv + b16c, inst16, vrow, it_ss);
+            int st_ss;
+            if constexpr (NOISE) {
+                // per-instance set points (mpc_loop_set_setpoints): the 16 lanes of an instance read its values, vector loads where the shared schedule's are scalar
+                // ones.  bi lies inside the padded stride in every lane (unused slots alias slot 0, a last partial wave reads the zero padding), and what such a
+                // lane computes from it reaches no live instance: the reductions of target_row16 stay inside the 16 lanes, every write below is guarded
+                double uspv[NU], yspv[NY];
+                MPC_UNROLL for (int i = 0; i < NU; i++) uspv[i] = a.usp[k * NU + i];
+                MPC_UNROLL for (int i = 0; i < NY; i++) yspv[i] = a.ysp[k * NY + i];
+                if (a.usp_b) { MPC_UNROLL for (int i = 0; i < NU; i++) uspv[i] = (a.usp_b + (size_t)((size_t)k * NU + i) * Bs)[bi]; }
+                if (a.ysp_b) { MPC_UNROLL for (int i = 0; i < NY; i++) yspv[i] = (a.ysp_b + (size_t)((size_t)k * NY + i) * Bs)[bi]; }
+                st_ss = target_row16<NX, NU, NY, ND, NGS, NHS>(P, r16, tab, uspv, yspv, dh, usv, kq + KC::K_TW, twv + b16c, inst16, vrow, it_ss);
+            } else
+                st_ss = target_row16<NX, NU, NY, ND, NGS, NHS>(P, r16, tab, a.usp + k * NU, a.ysp + k * NY, dh, usv, kq + KC::K_TW, twv + b16c, inst16, vrow, it_ss);
             // accept, or keep the previous target when infeasible (MPC_code.py:714-718); rows 0..NX-1 = xs, NX..NX+NU-1 = us
             const bool trow = r16 < NX + NU && b16 < NI;      // lanes of unused instance slots (NI < 4) alias slot 0: they must not write
             const double prev = trow ? kq[KC::K_XS + r16] : 0.0;      // K_XS.. and K_US.. are adjacent
@@ -749,6 +764,8 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
                 double usp[NU], ysp[NY], xs_n[NX], us_n[NU], ys_n[NY];
                 MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
                 MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
+                if (NOISE && a.usp_b) { MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = (a.usp_b + (size_t)((size_t)k * NU + i) * Bs)[bq]; }      // this instance's own set points
+                if (NOISE && a.ysp_b) { MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = (a.ysp_b + (size_t)((size_t)k * NY + i) * Bs)[bq]; }
                 int it_ss;
                 const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, kp + KC::K_TW, 1, twv + lane);
                 if (st_ss != kInfeasible) {
@@ -885,7 +902,8 @@ __global__ __launch_bounds__(64, 1) void loop_kernel_wv(const DevProblem *__rest
     loop_wv_body<false, NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>(Pp, a);
 }
 
-// ... and with the white noise: launched when a noise array is in force (another name, so that a listing's noise-free kernel is found by the name it always had)
+// ... and with per-instance step inputs (white noise, set points, or both): launched when one of their arrays is in force (another name, so that a listing's
+// shared-schedule, noise-free kernel is found by the name it always had)
 template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool MASKED, int NI, int NGS = 0, int NHS = 0>
 __global__ __launch_bounds__(64, 1) void loop_noisy_wv_kernel(const DevProblem *__restrict__ Pp, LoopArgs a)
 {
@@ -1043,7 +1061,7 @@ template <int NX, int NU, int NY, int ND, int NXP, bool DU, int NG, int NC, bool
 static int launch_loop_wv(const DevProblem *p, LoopArgs a, hipStream_t s, int dev)
 {
     using KC = WvKernelCfg<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
-    const bool noisy = a.vn || a.wn;      // (the entry whose body reads the noise arrays; the noise-free loop runs the one compiled without them)
+    const bool noisy = a.vn || a.wn || a.ysp_b || a.usp_b;      // (the entry whose body reads the per-instance arrays; the shared-schedule, noise-free loop runs the one compiled without them)
     auto kern = noisy ? loop_noisy_wv_kernel<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS> : loop_kernel_wv<NX, NU, NY, ND, NXP, DU, NG, NC, MASKED, NI, NGS, NHS>;
     static bool attr_set[2][64] = {};      // per entry and device: more than 64 KB of dynamic LDS has to be asked for
     if (!attr_set[noisy][dev]) {
@@ -1216,6 +1234,7 @@ struct mpc_handle {
     DevBuf pxy_in, pxy_lin, pxy_ws, off_px, off_py; int off_B = 0; bool off_has_px = false, off_has_py = false;
     DevBuf msch; int msch_steps = 0; bool msch_px = false, msch_py = false;      // def_px / def_py over the horizon for every step of the fused loop
     DevBuf noise_v, noise_w; int noise_steps = 0; bool has_vn = false, has_wn = false;      // white noise of the resident loop (mpc_loop_set_noise), [step][ny][Bs] / [step][nxp][Bs]
+    DevBuf sp_y, sp_u; int sp_steps = 0; bool has_ysp_b = false, has_usp_b = false;      // per-instance set points of the resident loop (mpc_loop_set_setpoints), [step][ny][Bs] / [step][nu][Bs]
     DevBuf st_x, st_xhat, st_dhat, st_P, st_u, st_xs, st_us, st_flag, st_Kg, st_Pn, st_tw, sch;
     LogTab log;                 // the logs mpc_loop_alloc enabled
     mpc_comm::State comm;       // multi-GPU (one process per GPU): the ranks of the job, staging buffers of the collectives
@@ -1543,7 +1562,7 @@ extern "C" void mpc_destroy(mpc_handle *h)
     h->pc_prev.release(); h->pc_valid.release(); h->pc_guess.release(); h->pc_traj.release();
     h->soft_ws.release(); h->soft_sl.release(); h->soft_keep.release();
     h->pxy_in.release(); h->pxy_lin.release(); h->pxy_ws.release(); h->off_px.release(); h->off_py.release(); h->msch.release();
-    h->noise_v.release(); h->noise_w.release();
+    h->noise_v.release(); h->noise_w.release(); h->sp_y.release(); h->sp_u.release();
     for (DevBuf *b : {&h->scratch, &h->ws, &h->st_x, &h->st_xhat, &h->st_dhat, &h->st_P, &h->st_u, &h->st_xs, &h->st_us, &h->st_flag, &h->st_Kg, &h->st_Pn, &h->st_tw, &h->sch}) b->release();
     if (h->dp) (void)hipFree(h->dp);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1968,6 +1987,7 @@ extern "C" int mpc_loop_alloc(mpc_handle *h, int32_t B, int32_t max_steps, int32
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->state_set = false; h->msch_steps = 0; h->msch_px = h->msch_py = false;
     h->noise_steps = 0; h->has_vn = h->has_wn = false;
+    h->sp_steps = 0; h->has_ysp_b = h->has_usp_b = false;
     if (ensure_ws(h, Bs)) return -10;
     const int sdim = P.ny + P.nu + P.nxp + P.ny;   // ysp usp pxp pyp
     if (h->sch.ensure((size_t)max_steps * sdim * 8)) return -10;
@@ -2067,6 +2087,7 @@ extern "C" int mpc_loop_set_schedule(mpc_handle *h, int32_t nsteps, const double
     if (pyp) std::memcpy(e, pyp, sizeof(double) * nsteps * P.ny);
     HIP_TRY(hipMemcpy(h->sch.p, st.data(), st.size() * 8, hipMemcpyHostToDevice));
     h->sched_steps = nsteps;
+    h->sp_steps = 0; h->has_ysp_b = h->has_usp_b = false;      // the last statement of the set points wins: per-instance arrays of an earlier mpc_loop_set_setpoints do not override this schedule
     return 0;
 }
 
@@ -2117,6 +2138,32 @@ extern "C" int mpc_loop_set_noise(mpc_handle *h, int32_t nsteps, const double *v
     return 0;
 }
 
+// Set points per step and per instance (the reference's defSP(t), MPC_code.py:677-680, evaluated by the caller for every instance): ysp [nsteps][B][ny],
+// usp [nsteps][B][nu]; a NULL array leaves that quantity on the shared schedule of mpc_loop_set_schedule, both NULL switch the feature off.  Step k of the
+// arrays is step k of the schedule.  Modelled on mpc_loop_set_noise: the stream is drained first, the buffers are allocated on the first call.
+extern "C" int mpc_loop_set_setpoints(mpc_handle *h, int32_t nsteps, const double *ysp, const double *usp)
+{
+    if (!h || h->B == 0) return fail(-1, "mpc_loop_alloc first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const DevProblem &P = h->hp;
+    if ((ysp || usp) && (nsteps < 1 || nsteps > h->max_steps))      // a refused call leaves the set points that were in force as they are
+        return fail(-1, "set points for %d steps, %d allocated", nsteps, h->max_steps);
+    h->sp_steps = 0; h->has_ysp_b = h->has_usp_b = false;      // (a HIP failure below leaves them off)
+    if (!ysp && !usp) return 0;
+    auto put = [&](DevBuf &buf, const double *src, int dim) -> int {
+        std::vector<double> st((size_t)nsteps * dim * h->Bs);
+        steps_to_soa(src, nsteps, h->B, dim, h->Bs, st.data());
+        if (buf.ensure(st.size() * 8)) return -10;
+        HIP_TRY(hipMemcpy(buf.p, st.data(), st.size() * 8, hipMemcpyHostToDevice));
+        return 0;
+    };
+    if (ysp) { if (int rc = put(h->sp_y, ysp, P.ny)) return rc; h->has_ysp_b = true; }
+    if (usp) { if (int rc = put(h->sp_u, usp, P.nu)) return rc; h->has_usp_b = true; }
+    h->sp_steps = nsteps;
+    return 0;
+}
+
 // Which closed-loop kernel: 1 = one instance per lane (loop_kernel; fills the chip from about 65536 instances),
 // 2 = horizon-parallel (loop_kernel_tp; one wave per instance, for batches that leave the chip idle otherwise).
 static int loop_mode(const mpc_handle *h)
@@ -2152,6 +2199,7 @@ extern "C" int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps)
     if (pxy && P.soft) return fail(-8, "soft constraints with horizon parameters (def_px / def_py) are not carried");
     const bool noisy = h->has_vn || h->has_wn;
     if (noisy && k0 + nsteps > h->noise_steps) return fail(-1, "steps [%d,%d) outside the noise of %d steps", k0, k0 + nsteps, h->noise_steps);
+    if ((h->has_ysp_b || h->has_usp_b) && k0 + nsteps > h->sp_steps) return fail(-1, "steps [%d,%d) outside the per-instance set points of %d steps", k0, k0 + nsteps, h->sp_steps);
     const int mode = pxy ? 5 : (P.soft ? 6 : loop_mode(h));
     if (mode != h->ws_mode) {      // the workspace holds another layout (or a per-call solve used it): next OCPs start cold
         HIP_TRY(hipMemsetAsync(h->st_flag.p, 0, 3 * Bs * 4, h->stream));
@@ -2168,6 +2216,8 @@ extern "C" int mpc_loop_run(mpc_handle *h, int32_t k0, int32_t nsteps)
         a.pxp = sch + ms * (P.ny + P.nu) + (size_t)k * P.nxp; a.pyp = sch + ms * (P.ny + P.nu + P.nxp) + (size_t)k * P.ny;
         a.vn = h->has_vn ? (const double *)h->noise_v.p + (size_t)k * P.ny * Bs : nullptr;
         a.wn = h->has_wn ? (const double *)h->noise_w.p + (size_t)k * P.nxp * Bs : nullptr;
+        a.ysp_b = h->has_ysp_b ? (const double *)h->sp_y.p + (size_t)k * P.ny * Bs : nullptr;
+        a.usp_b = h->has_usp_b ? (const double *)h->sp_u.p + (size_t)k * P.nu * Bs : nullptr;
         auto dl = [&](const char *nm) -> double * { return (double *)h->log.dev(nm, k); };      // (nullptr: a log that is not enabled)
         auto il = [&](const char *nm) -> int32_t * { return (int32_t *)h->log.dev(nm, k); };
         a.U = dl("U"); a.XHAT = dl("X_HAT"); a.XS = dl("XS"); a.US = dl("US"); a.YS = dl("YS"); a.XP = dl("Xp"); a.DHAT = dl("D_HAT");

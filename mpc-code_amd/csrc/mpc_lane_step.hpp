@@ -46,7 +46,9 @@ struct LoopArgs {
     double *lin;                                     // loop_kernel_pxy: slab of per-block stage data
     double *SL, *soft_ws, *sl_keep;                  // loop_kernel_soft: log of the slacks [step][2 ny][Bs] offset to k0 (or nullptr), the arrowhead solver's workspace, the last accepted slacks [2 ny][Bs]
     const double *vn, *wn;                           // white noise per step and instance (mpc_loop_set_noise), [step][ny][Bs] on the measurement and [step][nxp][Bs] on the
-                                                     // plant state after its step, offset to k0; nullptr: none (MPC_code.py:537-541, 822-827).  Last: the fields above keep their places
+                                                     // plant state after its step, offset to k0; nullptr: none (MPC_code.py:537-541, 822-827).  The fields above keep their places
+    const double *ysp_b, *usp_b;                     // set points per step and instance (mpc_loop_set_setpoints), [step][ny][Bs] / [step][nu][Bs], offset to k0; nullptr: that quantity
+                                                     // is the shared schedule's (ysp / usp above).  Last: the fields above keep their places
 };
 
 namespace mpc {
@@ -154,7 +156,8 @@ __device__ __forceinline__ void lane_estimate(const PT &P, const LoopArgs &a, in
 
 // ---- target (MPC_code.py:693-718): keep the previous one when infeasible; logs XS, US ------------------------------------------------
 // warm: the warm-start slot a.tw / a.tw_valid of the target solve (cold, like the per-call entry point, otherwise).  px0 / py0 (or nullptr):
-// p_x_k, p_y_k in the equalities; they reach target_lane with or without the warm start.
+// p_x_k, p_y_k in the equalities; they reach target_lane with or without the warm start.  The set points are the shared schedule's row k, or - a.ysp_b / a.usp_b -
+// this instance's own: the only place of these kernels that reads either.
 template <int NY, int ND, int NGS, int NHS, int NX, int NU, class PT>
 __device__ __forceinline__ int lane_target(const PT &P, const LoopArgs &a, int k, int b, const double *dh, double (&xs)[NX], double (&us)[NU], int &it_ss,
                                            bool warm, const double *px0 = nullptr, const double *py0 = nullptr)
@@ -162,6 +165,8 @@ __device__ __forceinline__ int lane_target(const PT &P, const LoopArgs &a, int k
     double usp[NU], ysp[NY], xs_n[NX], us_n[NU], ys_n[NY];
     MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = a.usp[k * NU + i];
     MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = a.ysp[k * NY + i];
+    if (a.usp_b) { MPC_UNROLL for (int i = 0; i < NU; i++) usp[i] = (a.usp_b + ((size_t)k * NU + i) * a.Bs)[b]; }      // this instance's own set points (mpc_loop_set_setpoints)
+    if (a.ysp_b) { MPC_UNROLL for (int i = 0; i < NY; i++) ysp[i] = (a.ysp_b + ((size_t)k * NY + i) * a.Bs)[b]; }
     const int st_ss = target_lane<NX, NU, NY, ND, NGS, NHS>(P, usp, ysp, dh, us, xs_n, us_n, ys_n, it_ss, warm ? a.tw + b : nullptr, warm ? a.Bs : 0,
                                                             warm ? a.tw_valid + b : nullptr, px0, py0);
     if (st_ss != kInfeasible) {

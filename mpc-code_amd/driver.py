@@ -42,8 +42,11 @@ def shard_noise(problem, nsteps: int, B: int, seed: int, total: Optional[int] = 
 
 def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None, solver: Optional[capi.Solver] = None,
                     fused: bool = True, device: int = 0, gather: bool = False, total: Optional[int] = None, comm=None,
-                    warm_start: bool = False, noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
-    """``noise_seed``: the example's white noises ``R_wn`` on every measurement and ``G_wn`` / ``Q_wn`` on the plant state after its step
+                    warm_start: bool = False, noise_seed: Optional[int] = None, setpoints: Optional[dict] = None) -> Dict[str, np.ndarray]:
+    """``setpoints``: every instance's own set-point schedule, a dict with ``ysp`` [nsteps, B, ny] and / or ``usp`` [nsteps, B, nu] for the ``B`` rows this call runs (a rank
+    of a sharded job passes its own rows, like ``x0_p``); what is not given stays on the example's shared schedule.  On the device through ``mpc_loop_set_setpoints``, in the
+    call-by-call mode row by row through ``mpc_target_solve``.  The result's ``YSP`` / ``USP`` [nsteps, B, .] are what was tracked.
+    ``noise_seed``: the example's white noises ``R_wn`` on every measurement and ``G_wn`` / ``Q_wn`` on the plant state after its step
     (``MPC_code.py:537-541, 822-827``; unseeded there), one draw per step and instance from ``numpy.random.default_rng(noise_seed)`` (:func:`shard_noise`); on the device
     through ``mpc_loop_set_noise``, on the host in the call-by-call mode.  ``Yp`` includes the measurement's noise; the draws come back as ``V_WN`` / ``W_WN``.
     ``gather=True``: this rank ran its shard of a batch of ``total`` instances; every result array is all-gathered over the
@@ -57,9 +60,10 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
     B = x0_p.shape[0]
     own = solver is None
     s = capi.Solver(p, device=device) if own else solver
-    noise_set = False
+    noise_set = sp_set = False
     try:
         sched = p.schedules(nsteps)
+        ysp_b, usp_b = capi.check_setpoints(setpoints, nsteps, B, p.ny, p.nu)
         vn = wn = None
         if noise_seed is not None:
             in_job = gather and total is not None and comm is not None
@@ -84,6 +88,9 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
             if noise_seed is not None:      # (without a seed the loop is noise-free, on a caller-owned solver too: the loop_alloc above cleared what its caller had installed)
                 s.loop_set_noise(vn, wn)
                 noise_set = True
+            if setpoints is not None:      # (after loop_set_schedule, which clears them)
+                s.loop_set_setpoints(ysp_b, usp_b)
+                sp_set = True
             s.loop_run(0, nsteps)
             s.loop_sync()
             out = {k: s.loop_get_log(k) for k in ("U", "X_HAT", "XS", "US", "YS", "Xp", "D_HAT", "STATUS_DYN",
@@ -100,7 +107,10 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
             ms, _ = s.last_kernel_ms()
             out["TIME_DYN"] = np.full(nsteps, ms * 1e-3 / nsteps); out["TIME_SS"] = np.zeros(nsteps)
         else:
+            if setpoints is not None:      # mpc_target_solve takes [B, .] rows: step k of the arrays where the shared schedule has its row k
+                sched = dict(sched, **({"ysp": ysp_b} if ysp_b is not None else {}), **({"usp": usp_b} if usp_b is not None else {}))
             out = _stepwise(p, s, x0_p, x0_m, nsteps, sched, warm_start=warm_start, vn=vn, wn=wn)
+        out.update(capi.tracked_setpoints(p.schedules(nsteps), ysp_b, usp_b, nsteps, B))
         if vn is not None:
             out["V_WN"] = vn
         if wn is not None:
@@ -108,8 +118,11 @@ def run_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None,
     finally:
         if own:
             s.close()
-        elif noise_set:      # (also after an exception: a caller-owned solver does not keep this run's draws)
-            s.loop_set_noise(None, None)
+        else:      # (also after an exception: a caller-owned solver keeps neither this run's draws nor its set points)
+            if noise_set:
+                s.loop_set_noise(None, None)
+            if sp_set:
+                s.loop_set_setpoints(None, None)
     if gather:
         if total is None:
             if comm is not None and comm.world > 1:

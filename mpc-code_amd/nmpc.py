@@ -14,11 +14,12 @@ import numpy as np
 
 from . import nlcodegen
 from . import noise as _noise
-from .capi import MpcAmdError
+from .capi import MpcAmdError, check_setpoints, tracked_setpoints
 
 NMPC_EXPORTS = ("nmpc_create", "nmpc_destroy", "nmpc_last_error", "nmpc_build_info", "nmpc_alloc", "nmpc_set_state", "nmpc_set_schedule",
                 "nmpc_run", "nmpc_sync", "nmpc_get_log", "nmpc_last_kernel_ms", "nmpc_set_kernel", "nmpc_set_groups", "nmpc_get_kernel", "nmpc_time_kernels",
-                "nmpc_wave_kernel_ms", "nmpc_ekf_update", "nmpc_target_solve", "nmpc_ocp_solve", "nmpc_plant_step", "nmpc_set_noise", "nmpc_set_state_noise")
+                "nmpc_wave_kernel_ms", "nmpc_ekf_update", "nmpc_target_solve", "nmpc_ocp_solve", "nmpc_plant_step", "nmpc_set_noise", "nmpc_set_state_noise",
+                "nmpc_set_setpoints", "nmpc_target_solve_inst")
 
 _dp = ct.POINTER(ct.c_double)
 _ip = ct.POINTER(ct.c_int32)
@@ -48,6 +49,7 @@ def load_nmpc_library(path: str) -> ct.CDLL:
     lib.nmpc_set_schedule.argtypes = [vp, ct.c_int32, _dp, _dp, _dp, _dp]
     lib.nmpc_set_noise.argtypes = [vp, ct.c_int32, _dp]
     lib.nmpc_set_state_noise.argtypes = [vp, ct.c_int32, _dp]
+    lib.nmpc_set_setpoints.argtypes = [vp, ct.c_int32, _dp, _dp]
     lib.nmpc_run.argtypes = [vp, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_double]
     lib.nmpc_sync.argtypes = [vp]
     lib.nmpc_set_kernel.argtypes = [vp, ct.c_int32]
@@ -59,6 +61,7 @@ def load_nmpc_library(path: str) -> ct.CDLL:
     lib.nmpc_wave_kernel_ms.argtypes = [vp, ct.POINTER(ct.c_float), _ip]
     lib.nmpc_ekf_update.argtypes = [vp] + [_dp] * 5
     lib.nmpc_target_solve.argtypes = [vp] + [_dp] * 5 + [_ip] * 2
+    lib.nmpc_target_solve_inst.argtypes = [vp] + [_dp] * 5 + [_ip] * 2
     lib.nmpc_ocp_solve.argtypes = [vp] + [_dp] * 5 + [ct.c_int32, ct.c_double] + [_dp] * 2 + [_ip] * 3
     lib.nmpc_plant_step.argtypes = [vp] + [_dp] * 3
     _libs[path] = lib
@@ -156,6 +159,18 @@ class NmpcSolver:
                 raise ValueError(f"noise: [nsteps, {self.B}, {d}] expected, got {a.shape}")
             self._chk(fn(self.h, a.shape[0], a.ctypes.data_as(_dp)), what)
 
+    def set_setpoints(self, ysp=None, usp=None):
+        """set points per step and per instance: ``ysp`` [nsteps, B, ny], ``usp`` [nsteps, B, nu] (``defSP(t)`` of every instance, MPC_code.py:677-680), step k of the arrays
+        being step k of the schedule; None leaves that quantity on the shared schedule, both None: off.  A later ``set_schedule`` clears them."""
+        arrs = [None if a is None else _c(a) for a in (ysp, usp)]
+        for a, d in zip(arrs, (self.p.ny, self.p.nu)):
+            if a is not None and (a.ndim != 3 or a.shape[1:] != (self.B, d)):
+                raise ValueError(f"set points: [nsteps, {self.B}, {d}] expected, got {a.shape}")
+        n = next((a.shape[0] for a in arrs if a is not None), 0)
+        if any(a is not None and a.shape[0] != n for a in arrs):
+            raise ValueError("set points: ysp and usp cover the same number of steps")
+        self._chk(self.lib.nmpc_set_setpoints(self.h, int(n), *[None if a is None else a.ctypes.data_as(_dp) for a in arrs]), "nmpc_set_setpoints")
+
     # ---- per-call seam: the reference's three solver calls of a step (include/mpc_nmpc.h) --------------------------------------------------
     def ekf_update(self, y, u_prev, xhat, dhat, P):
         """defEstimator(..., 'ekf' | 'lue') for the batch (MPC_code.py:577-650); returns the posterior ``xhat, dhat, P``"""
@@ -167,14 +182,21 @@ class NmpcSolver:
         self._chk(self.lib.nmpc_ekf_update(self.h, *[v.ctypes.data_as(_dp) for v in (y, u, xh, dh, Pk)]), "nmpc_ekf_update")
         return xh, dh, Pk
 
-    def target_solve(self, dhat, ysp, usp, xs, us):
-        """solver_ss(...) for the batch (MPC_code.py:693-718): the targets of the step before in, this step's out; returns ``xs, us, status, sqp``"""
+    def target_solve(self, dhat, ysp, usp, xs, us, per_instance: bool = False):
+        """solver_ss(...) for the batch (MPC_code.py:693-718): the targets of the step before in, this step's out; returns ``xs, us, status, sqp``.
+        ``per_instance``: ``ysp`` [B, ny] and ``usp`` [B, nu] are every instance's own set points of this step (``nmpc_target_solve_inst``), not one row for all."""
         p, B = self.p, self.B
         dh, xs, us = _rows(dhat, B, max(p.nd, 1)), _rows(xs, B, p.nx).copy(), _rows(us, B, p.nu).copy()
-        ysp, usp = _c(ysp).reshape(p.ny), _c(usp).reshape(p.nu)
+        if per_instance:
+            ysp, usp = _c(ysp), _c(usp)
+            if ysp.shape != (B, p.ny) or usp.shape != (B, p.nu):
+                raise ValueError(f"target_solve(per_instance=True): ysp [{B}, {p.ny}] and usp [{B}, {p.nu}] expected, got {ysp.shape} and {usp.shape}")
+        else:
+            ysp, usp = _c(ysp).reshape(p.ny), _c(usp).reshape(p.nu)
         st, sq = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
-        self._chk(self.lib.nmpc_target_solve(self.h, dh.ctypes.data_as(_dp), ysp.ctypes.data_as(_dp), usp.ctypes.data_as(_dp), xs.ctypes.data_as(_dp), us.ctypes.data_as(_dp),
-                                             st.ctypes.data_as(_ip), sq.ctypes.data_as(_ip)), "nmpc_target_solve")
+        fn, what = (self.lib.nmpc_target_solve_inst, "nmpc_target_solve_inst") if per_instance else (self.lib.nmpc_target_solve, "nmpc_target_solve")
+        self._chk(fn(self.h, dh.ctypes.data_as(_dp), ysp.ctypes.data_as(_dp), usp.ctypes.data_as(_dp), xs.ctypes.data_as(_dp), us.ctypes.data_as(_dp),
+                     st.ctypes.data_as(_ip), sq.ctypes.data_as(_ip)), what)
         return xs, us, st, sq
 
     def ocp_solve(self, xhat, dhat, xs, us, u_prev, max_sqp: int = 1, sqp_tol: float = 1e-9):
@@ -259,10 +281,11 @@ def path_noise(problem, nsteps: int, B: int, seed: int):
 
 
 def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None, solver: Optional[NmpcSolver] = None, max_sqp: int = 1, sqp_tol: float = 1e-9,
-                      device: int = 0, plant=None, noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
+                      device: int = 0, plant=None, noise_seed: Optional[int] = None, setpoints: Optional[dict] = None) -> Dict[str, np.ndarray]:
     """The reference's loop body call by call (MPC_code.py:485-827): per step the measurement (the Ex-file's plant output on the host), ``ekf_update``
     (defEstimator), ``target_solve`` (solver_ss), ``ocp_solve`` (solver) and the plant - ``plant(x_p [B, nxp], u [B, nu], t) -> x_p+`` of the caller, or the
     device's.  With the device's plant: :func:`run_nmpc_closed_loop` on the instance-per-lane kernel to the bit (when the plant output is exact on the host).
+    ``setpoints``: as :func:`run_nmpc_closed_loop`'s; the rows of step k go to ``target_solve(..., per_instance=True)``.
     ``noise_seed``: the white noise of the example's ``R_wn`` on every measurement, ``y_k += sqrtm(R_wn) N(0, I)`` (MPC_code.py:538-541; unseeded there), one draw per
     step and instance from ``numpy.random.default_rng(noise_seed)``; the draws come back as ``V_WN`` [nsteps, B, ny].  With ``G_wn / Q_wn`` also the state noise,
     ``x_p <- (Fx_p + pxp_k) + G_wn sqrtm(Q_wn) N(0, I)`` (:822-827), added here on the caller's side of the seam and returned as ``W_WN`` [nsteps, B, nxp]."""
@@ -274,6 +297,7 @@ def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = Non
     own = solver is None
     s = NmpcSolver(p, device=device) if own else solver
     try:
+        ysp_b, usp_b = check_setpoints(setpoints, nsteps, B, p.ny, p.nu)
         s.alloc(B, 1)
         s.set_state(x_p, x0_m)
         sch = p.schedules(nsteps)
@@ -291,7 +315,11 @@ def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = Non
             if vn is not None:                                               # :537-541
                 y = y + vn[k]
             xhat, dhat, P = s.ekf_update(y, u, xhat, dhat, P)
-            xs, us, st_s, sq_s = s.target_solve(dhat, sch["ysp"][k], sch["usp"][k], xs, us)
+            if setpoints is not None:
+                xs, us, st_s, sq_s = s.target_solve(dhat, ysp_b[k] if ysp_b is not None else _rows(sch["ysp"][k], B, p.ny),
+                                                    usp_b[k] if usp_b is not None else _rows(sch["usp"][k], B, p.nu), xs, us, per_instance=True)
+            else:
+                xs, us, st_s, sq_s = s.target_solve(dhat, sch["ysp"][k], sch["usp"][k], xs, us)
             u, xhat, st_d, it_d, sq_d = s.ocp_solve(xhat, dhat, xs, us, u, max_sqp, sqp_tol)
             x_p = s.plant_step(u, x_p, sch["pxp"][k]) if plant is None else np.asarray(plant(x_p, u, t), dtype=np.float64) + sch["pxp"][k]
             if wn is not None:                                               # :822-827
@@ -299,6 +327,7 @@ def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = Non
             for kk, v in (("U", u), ("XS", xs), ("US", us), ("D_HAT", dhat[:, :p.nd]), ("STATUS_DYN", st_d), ("STATUS_SS", st_s), ("ITERS_DYN", it_d), ("SQP_DYN", sq_d), ("SQP_SS", sq_s)):
                 out[kk].append(np.array(v))
         res = {k: np.stack(v) for k, v in out.items() if not (k == "D_HAT" and p.nd == 0)}
+        res.update(tracked_setpoints(sch, ysp_b, usp_b, nsteps, B))
         if vn is not None:
             res["V_WN"] = vn
         if wn is not None:
@@ -310,8 +339,10 @@ def run_nmpc_stepwise(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = Non
 
 
 def run_nmpc_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = None, solver: Optional[NmpcSolver] = None,
-                         max_sqp: int = 1, sqp_tol: float = 1e-9, device: int = 0, noise_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
-    """``noise_seed``: white noise of the example's ``R_wn`` on every measurement and of its ``G_wn / Q_wn`` on the plant state after its step (:func:`path_noise`;
+                         max_sqp: int = 1, sqp_tol: float = 1e-9, device: int = 0, noise_seed: Optional[int] = None, setpoints: Optional[dict] = None) -> Dict[str, np.ndarray]:
+    """``setpoints``: every instance's own set-point schedule, a dict with ``ysp`` [nsteps, B, ny] and / or ``usp`` [nsteps, B, nu] for the ``B`` rows this call runs; what is
+    not given stays on the example's shared schedule (``nmpc_set_setpoints``).  The result's ``YSP`` / ``USP`` [nsteps, B, .] are what was tracked.
+    ``noise_seed``: white noise of the example's ``R_wn`` on every measurement and of its ``G_wn / Q_wn`` on the plant state after its step (:func:`path_noise`;
     returned as ``V_WN`` / ``W_WN``; on the device: ``nmpc_set_noise``, ``nmpc_set_state_noise``); None: the deterministic loop.
     ``max_sqp = 1``: one real-time iteration per step (one linearisation along the shifted previous trajectory, one QP);
     larger: iterate each OCP to the NLP's KKT point, what the reference's IPOPT call returns (``MPC_code.py:775-783``).
@@ -323,10 +354,15 @@ def run_nmpc_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = 
     B = x0_p.shape[0]
     own = solver is None
     s = NmpcSolver(p, device=device) if own else solver
+    sp_set = False
     try:
+        ysp_b, usp_b = check_setpoints(setpoints, nsteps, B, p.ny, p.nu)
         s.alloc(B, nsteps)
         s.set_state(x0_p, x0_m)
         s.set_schedule(p.schedules(nsteps))
+        if setpoints is not None:      # (after set_schedule, which clears them)
+            s.set_setpoints(ysp_b, usp_b)
+            sp_set = True
         vn, wn = path_noise(p, nsteps, B, noise_seed) if noise_seed is not None else (None, None)
         if noise_seed is not None:      # (a caller-owned solver keeps the noise its caller installed)
             s.set_noise(vn, wn)
@@ -337,6 +373,7 @@ def run_nmpc_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = 
             out["V_WN"] = vn
         if wn is not None:
             out["W_WN"] = wn
+        out.update(tracked_setpoints(p.schedules(nsteps), ysp_b, usp_b, nsteps, B))
         ms = s.last_kernel_ms()
         out["TIME_DYN"] = np.full(nsteps, ms * 1e-3 / nsteps); out["TIME_SS"] = np.zeros(nsteps)
         u_prev = np.concatenate([_rows(p.u0, B, p.nu)[None], out["U"][:-1]]) if nsteps else out["U"]
@@ -349,6 +386,9 @@ def run_nmpc_closed_loop(problem, x0_p=None, x0_m=None, nsteps: Optional[int] = 
     finally:
         if own:
             s.close()
-        elif noise_seed is not None:      # (also after an exception)
-            s.set_noise(None)
+        else:      # (also after an exception: a caller-owned solver keeps neither this run's draws nor its set points)
+            if noise_seed is not None:
+                s.set_noise(None)
+            if sp_set:
+                s.set_setpoints(None, None)
     return out

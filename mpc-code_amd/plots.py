@@ -24,7 +24,8 @@ def _figure(plt, t, series, label, k, path, steps=False, legend=None):
 
 
 def make_plots(out: Dict[str, np.ndarray], h: float, path: str, instance: int = 0, ysp: Optional[np.ndarray] = None) -> List[str]:
-    """``out``: the result arrays of a closed-loop run ([nsteps, B, dim], names of MPC_code.py:877-895); ``h``: the sampling time; returns the files written."""
+    """``out``: the result arrays of a closed-loop run ([nsteps, B, dim], names of MPC_code.py:877-895); ``h``: the sampling time; returns the files written.
+    ``ysp`` [nsteps, ny]: the set point of the instance drawn (its column of a run's ``YSP``), a third curve of the output figures."""
     import matplotlib
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt

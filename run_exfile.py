@@ -8,7 +8,9 @@ Loads the file unmodified (mpc-code_amd/exfile.py), runs the closed loop of MPC_
 (mpc_code_amd.run_example) and stores the reference's result arrays (U, X_HAT, XS, US, Xp, ... : [nsteps, batch, dim]) in an .npz; prints a
 summary line per array.  `--batch B --spread s`: B instances whose plant and model start states are the file's own times (1 + s U(-1, 1))
 (s = 0: B copies).  `--noise-seed S`: the file's white noises (R_wn on the measurements, G_wn / Q_wn on the plant state), drawn from
-numpy.random.default_rng(S) - without it the loops run noise-free; the draws are stored as V_WN / W_WN.  `-o NAME=VALUE` overrides a variable of the file (a Python literal), e.g. the horizons of the BASELINE configurations."""
+numpy.random.default_rng(S) - without it the loops run noise-free; the draws are stored as V_WN / W_WN.  `--setpoints FILE.npz`: every
+instance's own set-point schedule, arrays `ysp` [nsteps, batch, ny] and / or `usp` [nsteps, batch, nu] (what is missing stays on the file's defSP); the tracked values are stored as
+YSP / USP, and `--plots --instance i` draws instance i's own.  `-o NAME=VALUE` overrides a variable of the file (a Python literal), e.g. the horizons of the BASELINE configurations."""
 import argparse
 import ast
 import os
@@ -29,6 +31,7 @@ def main(argv=None):
     ap.add_argument("--nsteps", type=int, default=None, help="default: the file's Nsim")
     ap.add_argument("--max-sqp", type=int, default=None, help="non-linear tracking path: SQP iterations per OCP (default 1: real-time iteration)")
     ap.add_argument("--noise-seed", type=int, default=None, help="simulate the file's white noises R_wn, G_wn / Q_wn with this seed (default: noise-free)")
+    ap.add_argument("--setpoints", default=None, metavar="FILE.npz", help="per-instance set points: arrays ysp [nsteps, batch, ny] and / or usp [nsteps, batch, nu]")
     ap.add_argument("-o", "--override", action="append", default=[], metavar="NAME=VALUE")
     ap.add_argument("--out", default=None, help="write the result arrays to this .npz")
     ap.add_argument("--load-only", action="store_true", help="load and classify the file, then stop (no GPU needed)")
@@ -42,6 +45,18 @@ def main(argv=None):
         over[k.strip()] = ast.literal_eval(v)
     p = m.load_problem(a.exfile, overrides=over or None)
     print(f"{os.path.basename(a.exfile)}: {type(p).__name__}, nx={p.nx} nu={p.nu} ny={p.ny} nd={p.nd} N={p.N}" + (f" N_mhe={p.N_mhe}" if hasattr(p, "N_mhe") else ""))
+    setpoints = None
+    if a.setpoints:      # (checked before anything runs, and with --load-only too: shapes against --batch and --nsteps)
+        if isinstance(p, m.EconomicMPCProblem):
+            raise SystemExit("--setpoints: the economic path has no set points")
+        from mpc_code_amd.capi import check_setpoints
+        with np.load(a.setpoints) as f:
+            setpoints = {k: np.asarray(f[k], dtype=float) for k in f.files}
+        try:
+            check_setpoints(setpoints, p.Nsim if a.nsteps is None else a.nsteps, a.batch, p.ny, p.nu)
+        except ValueError as e:
+            raise SystemExit(f"--setpoints {a.setpoints}: {e}")
+        print(f"  set points per instance: {', '.join(f'{k} {v.shape}' for k, v in setpoints.items())}")
     if a.load_only:
         return 0
     rng = np.random.default_rng(a.seed)
@@ -49,6 +64,8 @@ def main(argv=None):
     kw = {}
     if a.noise_seed is not None:      # (every path's loop takes it: driver.run_closed_loop, nmpc.run_nmpc_closed_loop, enmpc.run_enmpc_closed_loop)
         kw["noise_seed"] = a.noise_seed
+    if setpoints is not None:
+        kw["setpoints"] = setpoints
     if isinstance(p, m.EconomicMPCProblem):
         out = m.run_example(p, x0_p=x0p, nsteps=a.nsteps, **kw)
     else:
@@ -64,7 +81,7 @@ def main(argv=None):
             print(f"  {k:10s} {str(v.shape):18s} values {np.unique(v).tolist()[:8]}")
     if a.plots:
         from mpc_code_amd.plots import make_plots
-        files = make_plots(out, float(p.h), a.plots, instance=a.instance)
+        files = make_plots(out, float(p.h), a.plots, instance=a.instance, ysp=np.asarray(out["YSP"])[:, a.instance] if setpoints is not None else None)      # (that instance's own set point)
         print(f"wrote {len(files)} figures under {a.plots}")
     if a.out:
         np.savez_compressed(a.out, **{k: np.asarray(v) for k, v in out.items()})
