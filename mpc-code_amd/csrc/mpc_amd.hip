@@ -574,7 +574,7 @@ __device__ __forceinline__ bool wv_term_aim(int N, double *q, int *iflag, int *a
             aimv[j] = again ? 1 : 0;
         }
     }
-    __syncthreads();
+    wave_lds_sync();
     int any = 0;
     MPC_UNROLL for (int j = 0; j < NI; j++) any |= aimv[j];
     any = __builtin_amdgcn_readfirstlane(any);
@@ -584,7 +584,7 @@ __device__ __forceinline__ bool wv_term_aim(int N, double *q, int *iflag, int *a
         const int f = iflag[lane];
         if ((f & kWvValid) && (f & kWvOk0) && st != kInfeasible) { iflag[lane] = kWvValid | kWvOk0 | kWvWarm | kWvNoShift; itacc[lane] += it; }
     }
-    __syncthreads();
+    wave_lds_sync();
     return any != 0;
 }
 
@@ -605,7 +605,7 @@ struct WvKernelCfg {
     // instance data behind it), so the region is the larger of the two.
     static constexpr int t_region(int N)
     {
-        const int t = Cfg::t_doubles(N), x = Cfg::GUARD + (RT::fits ? 4 * RT::XCH : 0);
+        const int t = Cfg::t_doubles(N), x = Cfg::T_OFF + (RT::fits ? 4 * RT::XCH : 0);
         return t > x ? t : x;
     }
     static constexpr size_t lds_bytes(int N) { return sizeof(double) * ((size_t)t_region(N) + NI * Cfg::QN + NI * Cfg::OUT + NI * KEEP + (RT::fits ? RT::DOUBLES : 0)) + sizeof(int) * 24; }
@@ -626,7 +626,7 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
     extern __shared__ double wv_smem[];
     const DevProblem &P0 = *Pp;
     const int LD = Cfg::ld(P0.N);
-    double *const T = wv_smem + Cfg::GUARD, *const q = wv_smem + KC::t_region(P0.N), *const outv = q + NI * Cfg::QN, *const keep = outv + NI * Cfg::OUT;
+    double *const T = wv_smem + Cfg::T_OFF, *const q = wv_smem + KC::t_region(P0.N), *const outv = q + NI * Cfg::QN, *const keep = outv + NI * Cfg::OUT;
     int *const iflag = (int *)(keep + NI * KEEP), *const twv = iflag + 4, *const wsv = twv + 4, *const aimv = wsv + 4, *const itacc = aimv + 4;      // (terminal equality: wv_term_aim)
     using RT = typename KC::RT;
     double *const tab = (double *)(wsv + 16);      // per-row constants of the 16-lanes-per-instance phases
@@ -649,9 +649,10 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
         twv[lane] = a.tw_valid[b]; wsv[lane] = a.ws_valid[b];
     } else if (lane < NI) { twv[lane] = 0; wsv[lane] = 0; }
     for (int i = lane; i < NI * LD; i += 64) T[Cfg::RZ * NI * LD + i] = 0.0;      // the zero row of the tile view
-    if (lane < Cfg::GUARD) wv_smem[lane] = 0.0;
+    if (lane < Cfg::GUARD) wv_smem[Cfg::TCN + lane] = 0.0;
+    wv_fill_tile_consts<NS, NU, DU, NC, NI>(P, wv_smem, lane);
     if (RT::fits) row16_fill_tables<NX, NU, NY, ND, NGS, NHS>(P, tab, lane);
-    __syncthreads();
+    wave_lds_sync();
     // resident iterates: the warm start of a previous launch (inputs and bound multipliers), lane = block
     WvIterA<NS, NU, NC> X[NI];
     WvInst S[NI];
@@ -673,7 +674,8 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
         if constexpr (RT::fits) {
             // ---- estimator and target with 16 lanes per instance (mpc_wave.hpp) --------------------------------------
             const int b16 = lane >> 4, r16 = lane & 15, b16c = b16 < NI ? b16 : 0;
-            const unsigned bi = (unsigned)(blockIdx.x * NI + b16c);
+            unsigned bi = (unsigned)(blockIdx.x * NI + b16c);
+            asm volatile("" : "+v"(bi));      // (opaque per step, as bq: hoisted out of the step loop the addresses of the log arrays occupy accumulation registers)
             const bool inst16 = b16 < NI && (int)bi < a.B;
             double *const kq = keep + b16c * KEEP;
             if (inst16) {
@@ -685,7 +687,7 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
                 kalman_row16<NX, NY, ND, NXP, NU>(P, r16, b16 < NI, kq, KC::K_X, KC::K_XH, KC::K_P, a.pyp + k * NY, (NOISE && a.vn) ? a.vn + (size_t)k * NY * Bs + bi : nullptr, Bs, tab, T + b16c * RT::XCH, xi_old, xi_new);
             if (inst16 && a.DHAT && r16 >= NX && r16 < NE) (a.DHAT + (size_t)((size_t)k * ND + (r16 - NX)) * Bs)[bi] = xi_new;
             double delta = row16_max(r16 < NE ? fabs(xi_new - xi_old) : 0.0);      // warm-start test: estimate against its prediction
-            __syncthreads();
+            wave_lds_sync();
             // (the estimator's exchange area is the start of T: with a very short horizon it reaches the zero row of the tile view)
             if (Cfg::RZ * NI * LD < 4 * RT::XCH) { for (int i = lane; i < NI * LD; i += 64) T[Cfg::RZ * NI * LD + i] = 0.0; }
             double dh[NDD], usv[NU];
@@ -717,7 +719,7 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
                 if (a.st_dyn && r16 == 0) { (a.st_ss + (size_t)k * Bs)[bi] = st_ss; (a.it_ss + (size_t)k * Bs)[bi] = it_ss; }
             }
             if (r16 == 0 && b16 < NI) outv[b16c * Cfg::OUT] = delta;
-            __syncthreads();
+            wave_lds_sync();
         }
         if (valid) {
             double xh[NX], dh[NDD], u[NU], xs[NX], us[NU], delta = 0.0;
@@ -800,7 +802,7 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
             MPC_UNROLL for (int i = 0; i < ND; i++) kp[KC::K_DH + i] = dh[i];
             MPC_UNROLL for (int i = 0; i < NU; i++) kp[KC::K_US + i] = us[i];
         } else if (lane < NI) iflag[lane] = 0;
-        __syncthreads();
+        wave_lds_sync();
         }
         MPC_TSTAMP(0);
         wv_solve<NS, NU, DU, NC, MASKED, NI>(P, T, q, iflag, X, S, P.max_iter);
@@ -824,7 +826,7 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
                 aimv[j] = again ? 1 : 0;
             }
         }
-        __syncthreads();
+        wave_lds_sync();
         if (P.term_cons && redo < 2) {
             int any = 0;
             MPC_UNROLL for (int j = 0; j < NI; j++) any |= aimv[j];
@@ -835,7 +837,7 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
                     const int f = iflag[lane];
                     if ((f & kWvValid) && (f & kWvOk0) && st != kInfeasible) { iflag[lane] = kWvValid | kWvOk0 | kWvWarm | kWvNoShift; itacc[lane] += it; }
                 }
-                __syncthreads();
+                wave_lds_sync();
                 redo++; k--;
                 continue;
             }
@@ -877,7 +879,7 @@ __device__ __forceinline__ void loop_wv_body(const DevProblem *__restrict__ Pp, 
             MPC_UNROLL for (int i = 0; i < NU; i++) kp[KC::K_U + i] = u[i];
             wsv[lane] = st_dyn == kSolved ? 1 : 0;
         }
-        __syncthreads();
+        wave_lds_sync();
         MPC_TSTAMP(7);
     }
     if (valid) {
@@ -932,7 +934,7 @@ __global__ __launch_bounds__(64, 1) void ocp_kernel_wv(const DevProblem *__restr
     extern __shared__ double wv_smem[];
     const ConstProblem &P = *(const ConstProblem *)Pp;
     const int N = Pp->N, LD = Cfg::ld(N);
-    double *const T = wv_smem + Cfg::GUARD, *const q = wv_smem + Cfg::t_doubles(N), *const outv = q + NI * Cfg::QN;
+    double *const T = wv_smem + Cfg::T_OFF, *const q = wv_smem + Cfg::t_doubles(N), *const outv = q + NI * Cfg::QN;
     int *const iflag = (int *)(outv + NI * Cfg::OUT), *const aimv = iflag + 4, *const itacc = aimv + 4;
     const size_t Bs = a.Bs;
     const int lane = threadIdx.x;
@@ -940,7 +942,8 @@ __global__ __launch_bounds__(64, 1) void ocp_kernel_wv(const DevProblem *__restr
     const int b = blockIdx.x * NI + il;
     const bool valid = lane < NI && b < a.B;
     for (int i = lane; i < NI * LD; i += 64) T[Cfg::RZ * NI * LD + i] = 0.0;
-    if (lane < Cfg::GUARD) wv_smem[lane] = 0.0;
+    if (lane < Cfg::GUARD) wv_smem[Cfg::TCN + lane] = 0.0;
+    wv_fill_tile_consts<NS, NU, DU, NC, NI>(P, wv_smem, lane);
     if (valid) {
         double xh[NX], xs[NX], us[NU], up[NU], dh[NDD];
         MPC_UNROLL for (int i = 0; i < NX; i++) { xh[i] = a.xhat[i * Bs + b]; xs[i] = a.xs[i * Bs + b]; }
@@ -964,7 +967,7 @@ __global__ __launch_bounds__(64, 1) void ocp_kernel_wv(const DevProblem *__restr
         MPC_UNROLL for (int i = 0; i < NX; i++) w.prev[(NX + ND + i) * Bs + b] = xs[i];
         MPC_UNROLL for (int i = 0; i < NU; i++) w.prev[(2 * NX + ND + i) * Bs + b] = us[i];
     } else if (lane < NI) iflag[lane] = 0;
-    __syncthreads();
+    wave_lds_sync();
     WvIterA<NS, NU, NC> X[NI];
     WvInst S[NI];
     MPC_UNROLL for (int j = 0; j < NI; j++) {
@@ -1002,7 +1005,7 @@ __global__ __launch_bounds__(64, 1) void ocp_kernel_wv(const DevProblem *__restr
             outv[j * Cfg::OUT + NU + NS] = v;
         }
     }
-    __syncthreads();
+    wave_lds_sync();
     if (valid) {
         int st = S[0].status, it = S[0].iters; double r0 = S[0].res_s, r1 = S[0].res_p, r2 = S[0].mu;
         MPC_UNROLL for (int j = 1; j < NI; j++) { if (lane == j) { st = S[j].status; it = S[j].iters; r0 = S[j].res_s; r1 = S[j].res_p; r2 = S[j].mu; } }

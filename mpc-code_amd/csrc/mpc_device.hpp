@@ -98,10 +98,41 @@ __device__ unsigned long long mpc_stamp_buf[4096 * 8];
 
 __device__ __forceinline__ double dmax(double a, double b) { return __builtin_fmax(a, b); }   // v_max_f64, one instruction
 __device__ __forceinline__ double dmin(double a, double b) { return __builtin_fmin(a, b); }
+// The same maximum on two values that sit in vector registers, as the bare instruction.  __builtin_fmax quiets (v_max_f64 x, y, y) every
+// operand it cannot prove canonical - a DPP move's result, an accumulation register read back, a select, an LDS load - before the maximum
+// itself; the instruction does that on its own (IEEE mode: a quiet NaN operand is dropped, a signalling one quieted), so the result has
+// the same bits.  For the steps of the DPP reductions and for maxima / minima of the resident iterate's entries, whose operands are never
+// constants and carry no |x| modifier.
+__device__ __forceinline__ double dmax_vv(double a, double b)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double dmin_vv(double a, double b)
+{
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// Synchronisation inside a workgroup that is one wave (the wave-autonomous kernels): the lanes run in lock step and the LDS serves a
+// wave's accesses in order, so there is nothing to meet at - what is needed is that the LDS traffic issued so far has completed and
+// that the compiler moves no access across this point.  __syncthreads() also waits for every outstanding global access (vmcnt(0)): behind
+// the log stores of a step that is the round trip of their acknowledgements.  Not for kernels with more than one wave per workgroup.
+__device__ __forceinline__ void wave_lds_sync()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
 __device__ __forceinline__ bool fin(double a) { return fabs(a) < 1.0e300; }
 __device__ __forceinline__ double comp_measure(double s, double l)
 {
     return dmin(dmin(s, l) * (1.0 / kTolC), s * l * (1.0 / kTolMu));
+}
+
+// comp_measure on two values that sit in vector registers (dmin_vv): the same expression, the same bits
+__device__ __forceinline__ double comp_measure_vv(double s, double l)
+{
+    return dmin(dmin_vv(s, l) * (1.0 / kTolC), s * l * (1.0 / kTolMu));
 }
 
 // accurate reciprocal without the IEEE division sequence: v_rcp_f64 + two Newton steps (~1 ulp for normal x)

@@ -107,12 +107,12 @@ __device__ __forceinline__ double wave_sum(double v)
 }
 __device__ __forceinline__ double wave_max(double v)
 {
-    v = dmax(v, dpp_move<0xB1, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x4E, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x141, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x140, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x142, 0xA>(v, v));
-    v = dmax(v, dpp_move<0x143, 0xC>(v, v));
+    v = dmax_vv(v, dpp_move<0xB1, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x4E, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x141, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x140, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x142, 0xA>(v, v));
+    v = dmax_vv(v, dpp_move<0x143, 0xC>(v, v));
     return lane63(v);
 }
 // the same over each half of the wave (lanes 0-31 | 32-63), every lane getting its half's result: the first five steps of the tree
@@ -136,11 +136,11 @@ __device__ __forceinline__ double half_sum(double v)
 }
 __device__ __forceinline__ double half_max(double v)
 {
-    v = dmax(v, dpp_move<0xB1, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x4E, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x141, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x140, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x142, 0xA>(v, v));
+    v = dmax_vv(v, dpp_move<0xB1, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x4E, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x141, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x140, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x142, 0xA>(v, v));
     const double lo = lane_of(v, 31), hi = lane_of(v, 63);
     return (threadIdx.x & 32) ? hi : lo;
 }

@@ -49,11 +49,19 @@ struct WvCfg {
     // row stride: the horizon + 1, made odd: the tile view (row, instance) then hits distinct banks; 65 for the longest horizon
     __host__ __device__ static constexpr int ld(int N) { return (N + 1) | 1; }
     static constexpr int GUARD = 8;                                    // cells in front of T: look-ahead reads of the backward loops, stores of idle lanes
-    __host__ __device__ static constexpr int t_doubles(int N) { return GUARD + ROWS * NI * ld(N); }
+    // Tile constants (one-tile stages, NS <= 4): the problem's matrices A, Q, Pf, B, M, R each zero-padded to a 4 x 4 tile, at the very start of
+    // the wave's LDS (a compile-time address: no register holds it between the sweeps).  A lane of the tile view reads its element (row,
+    // column) of A, A', B, B', Q, R, Pf, M' from here at the head of a sweep (wv_fill_tile_consts writes them once per launch) - from the
+    // problem struct that is a gather by lane, i.e. vector loads from global memory and their round trip in front of every sweep.
+    // Stages of 2 x 2 tiles keep the gather: their table (272 doubles) would cost the largest sets a resident wave per CU at N = 64.
+    static constexpr bool TILE_TAB = NS <= 4;
+    static constexpr int TC_A = 0, TC_Q = 16, TC_P = 32, TC_B = 48, TC_M = 64, TC_R = 80, TCN = TILE_TAB ? 96 : 0;
+    static constexpr int T_OFF = TCN + GUARD;                          // T starts here
+    __host__ __device__ static constexpr int t_doubles(int N) { return T_OFF + ROWS * NI * ld(N); }
     // time-varying stage data (wv_solve<.., LTV>: one SQP iteration of the non-linear path): per (instance, block) the matrices
     // A_k (NS x NS), B_k (NS x NU) and the affine term c_k as rows behind the others (35 rows for ns = 3, nu = 2: four workgroups per CU at N = 30)
     static constexpr int RL_A = ROWS, RL_B = RL_A + NS * NS, RL_C = RL_B + NS * NU, ROWS_LTV = RL_C + NS;
-    __host__ __device__ static constexpr int t_doubles_ltv(int N) { return GUARD + ROWS_LTV * NI * ld(N); }
+    __host__ __device__ static constexpr int t_doubles_ltv(int N) { return T_OFF + ROWS_LTV * NI * ld(N); }
     static constexpr int QZN = 5 * NS + 2 * NU + 1;                    // reference of the terminal cost: zr, or (terminal equality) zr aimed off by the measured miss
     static constexpr int QN = QZN + NS;                                // z0 zr c zlo zhi | ur us | ws_delta | zrN
     static constexpr int ROWS_WS = NU + 2 * NC;                        // warm start kept in HBM between launches: u | l_lo | l_hi
@@ -106,6 +114,24 @@ struct WvInst { double mu, mu_sum, sm, inv_ncon, gscale, res_s, res_p; int stall
 
 enum : int { kWvOk0 = 1, kWvWarm = 2, kWvValid = 4, kWvKeepU = 8, kWvNoShift = 16 };      // NoShift: warm start from the iterate as it is (an SQP iteration of the same step)      // KeepU: warm start whose inputs are a caller's guess for THIS problem (not to be shifted)
 
+// The tile constants of WvCfg (tc = the start of the wave's LDS): once per launch, by every caller of wv_solve before its first solve,
+// with a synchronisation between this and the solve.  Entries outside the matrices are zeros, as the tile view pads them (the LDS
+// serves a wave's stores in order: the zeros first, then the elements).
+template <int NS, int NU, bool HASM, int NC, int NI, class PT>
+__device__ __forceinline__ void wv_fill_tile_consts(const PT &P, double *tc, int lane)
+{
+    using Cfg = WvCfg<NS, NU, NC, NI>;
+    if constexpr (Cfg::TILE_TAB) {
+        for (int e = lane; e < Cfg::TCN; e += 64) tc[e] = 0.0;
+        const int r = (lane >> 2) & 3, c = lane & 3;
+        if (lane < 16) {      // each matrix by its own shape: NS x NS, NS x NU, NU x NU (a stage may have fewer states than inputs)
+            if (r < NS && c < NS) { tc[Cfg::TC_A + lane] = P.A[r][c]; tc[Cfg::TC_Q + lane] = P.Q[r][c]; tc[Cfg::TC_P + lane] = P.Pf[r][c]; }
+            if (r < NS && c < NU) { tc[Cfg::TC_B + lane] = P.B[r][c]; if (HASM) tc[Cfg::TC_M + lane] = P.M[r][c]; }
+            if (r < NU && c < NU) tc[Cfg::TC_R + lane] = P.R[r][c];
+        }
+    }
+}
+
 // sums / maxima over the 16 lanes of a DPP row (= one instance of the target problem's constraint rows); result in every lane
 __device__ __forceinline__ double row16_sum(double v)
 {
@@ -117,10 +143,10 @@ __device__ __forceinline__ double row16_sum(double v)
 }
 __device__ __forceinline__ double row16_max(double v)
 {
-    v = dmax(v, dpp_move<0xB1, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x4E, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x141, 0xF>(v, v));
-    v = dmax(v, dpp_move<0x140, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0xB1, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x4E, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x141, 0xF>(v, v));
+    v = dmax_vv(v, dpp_move<0x140, 0xF>(v, v));
     return v;
 }
 
@@ -181,7 +207,10 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         MPC_UNROLL for (int i = 0; i < NU; i++) du[i] = Xj.u[i] - qd[5 * NS + i];
         MPC_UNROLL for (int i = 0; i < NS; i++) {
             double a = (NU + i < NC) ? Xj.lh[NU + i < NC ? NU + i : 0] - Xj.ll[NU + i < NC ? NU + i : 0] : 0.0;
-            MPC_UNROLL for (int l = 0; l < NS; l++) a += (last ? Pl.Pf[i][l] : Pl.Q[i][l]) * dz1[l];
+            // (both weights as values - two scalar loads - and the lane's one selected: a conditional between the two matrices themselves is
+            // a per-lane address, i.e. a vector load from global memory with its round trip in every phase that takes a gradient.  Two sums
+            // and a selected result hold more instructions, by the listing.)
+            MPC_UNROLL for (int l = 0; l < NS; l++) { const double wq = Pl.Q[i][l], wp = Pl.Pf[i][l]; a += (last ? wp : wq) * dz1[l]; }
             gz[i] = a;
         }
         MPC_UNROLL for (int i = 0; i < NU; i++) {
@@ -211,8 +240,9 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             if (blk_on) tk(RA + i, j) = Xj.ll[i] * isl + Xj.lh[i] * ish;      // lanes beyond the horizon would land in the next row (stride N + 1)
             hb[i] = Xj.lh[i] * (rh * ish - 1.0) + Xj.ll[i] * (rl * isl + 1.0);
             resp_p = dmax(resp_p, dmax(fabs(rl), fabs(rh)));
-            cres_p = dmax(cres_p, dmax(comp_measure(Xj.sl[i], Xj.ll[i]), comp_measure(Xj.sh[i], Xj.lh[i])));
-            lmax_p = dmax(lmax_p, dmax(Xj.ll[i], Xj.lh[i]));
+            // (on the iterate's entries as they come out of the accumulation registers: bare minima / maxima)
+            cres_p = dmax(cres_p, dmax(comp_measure_vv(Xj.sl[i], Xj.ll[i]), comp_measure_vv(Xj.sh[i], Xj.lh[i])));
+            lmax_p = dmax(lmax_p, dmax_vv(Xj.ll[i], Xj.lh[i]));
         }
         double gu[NU], gz[NS], pi[NS];
         gradient(Pl, j, Xj, gu, gz);
@@ -440,6 +470,19 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         double *p_hu, *p_hz[SB], *p_kf, *p_k[SB], *p_kt[SB], *p_li;
         const double *p_a, *p_at, *p_b, *p_bt;      // LTV: this lane's element of A_k, A_k', B_k, B_k' as a function of the block (rows of T)
     };
+    // Element (r, c) of the problem's matrices as the tile view pads them (zero outside the matrix): of a one-tile stage from the tile
+    // constants in LDS (wv_fill_tile_consts; r, c < 4), else gathered from the problem struct.
+    const double *const tcs = T - Cfg::T_OFF;
+    auto tile_el = [&](int tab, const auto &M, int nr, int nc, int r, int c) -> double {      // M: nr x nc, its table at tcs + tab
+        if constexpr (Cfg::TILE_TAB) return tcs[tab + 4 * r + c];
+        else return (r < nr && c < nc) ? M[r < nr ? r : 0][c < nc ? c : 0] : 0.0;
+    };
+    auto el_a = [&](const PT &Pl, int r, int c) -> double { return tile_el(Cfg::TC_A, Pl.A, NS, NS, r, c); };
+    auto el_q = [&](const PT &Pl, int r, int c) -> double { return tile_el(Cfg::TC_Q, Pl.Q, NS, NS, r, c); };
+    auto el_p = [&](const PT &Pl, int r, int c) -> double { return tile_el(Cfg::TC_P, Pl.Pf, NS, NS, r, c); };
+    auto el_b = [&](const PT &Pl, int r, int c) -> double { return tile_el(Cfg::TC_B, Pl.B, NS, NU, r, c); };
+    auto el_m = [&](const PT &Pl, int r, int c) -> double { return tile_el(Cfg::TC_M, Pl.M, NS, NU, r, c); };
+    auto el_r = [&](const PT &Pl, int r, int c) -> double { return tile_el(Cfg::TC_R, Pl.R, NU, NU, r, c); };
     auto tile_ctx = [&](const PT &Pl) {
         int lo = threadIdx.x;
         asm volatile("" : "+v"(lo));
@@ -453,14 +496,8 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         auto trow = [&](int row) -> double * { return c.Tt + (c.live ? row : RZ) * (NI * LD); };
         MPC_UNROLL for (int i = 0; i < SB; i++) {
             const int ri = 4 * i + tr, ci = 4 * i + tc;
-            MPC_UNROLL for (int j = 0; j < SB; j++) {
-                const int cj = 4 * j + tc, rj = 4 * j + tr;
-                c.Ar[i][j] = (ri < NS && cj < NS) ? Pl.A[ri < NS ? ri : 0][cj < NS ? cj : 0] : 0.0;
-                c.Atr[i][j] = (ri < NS && cj < NS) ? Pl.A[cj < NS ? cj : 0][ri < NS ? ri : 0] : 0.0;
-                (void)rj;
-            }
-            c.Br[i] = (ri < NS && tc < NU) ? Pl.B[ri < NS ? ri : 0][tc < NU ? tc : 0] : 0.0;
-            c.Btr[i] = (tr < NU && ci < NS) ? Pl.B[ci < NS ? ci : 0][tr < NU ? tr : 0] : 0.0;
+            MPC_UNROLL for (int j = 0; j < SB; j++) { c.Ar[i][j] = el_a(Pl, ri, 4 * j + tc); c.Atr[i][j] = el_a(Pl, 4 * j + tc, ri); }
+            c.Br[i] = el_b(Pl, ri, tc); c.Btr[i] = el_b(Pl, ci, tr);
             // vectors live in column-replicated tiles: hz rows of this lane; K (rows < NU, state columns) and K' as tiles
             c.p_hz[i] = trow(ri < NS ? RG + NU + ri : RZ);
             c.p_k[i] = trow((tr < NU && ci < NS) ? RA + tr * NS + ci : RZ);
@@ -486,17 +523,16 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         const int tr = c.tr, tc = c.tc; const bool live = c.live;
         double *const trash = c.trash;
         auto trow = [&](int row) -> double * { return c.Tt + (live ? row : RZ) * (NI * LD); };
-        const bool in_uu = tr < NU && tc < NU;
-        const double Rr = in_uu ? Pl.R[tr][tc] : 0.0;
+        const double Rr = el_r(Pl, tr, tc);
         double Qr[SB][SB], Mtr[SB], BE0[SB], BE1[SB];
         MPC_UNROLL for (int i = 0; i < SB; i++) {
             const int ri = 4 * i + tr, ci = 4 * i + tc;
-            MPC_UNROLL for (int j = 0; j < SB; j++) { const int cj = 4 * j + tc; Qr[i][j] = (ri < NS && cj < NS) ? Pl.Q[ri < NS ? ri : 0][cj < NS ? cj : 0] : 0.0; }
-            Mtr[i] = (HASM && tr < NU && ci < NS) ? Pl.M[ci < NS ? ci : 0][tr < NU ? tr : 0] : 0.0;
+            MPC_UNROLL for (int j = 0; j < SB; j++) Qr[i][j] = el_q(Pl, ri, 4 * j + tc);
+            Mtr[i] = HASM ? el_m(Pl, ci, tr) : 0.0;
             // rows 0 / 1 of Lambda = R~ + B'PB broadcast over all tile rows, straight from PB: (B E_i)' PB + E_i' R~
-            BE0[i] = ri < NS ? Pl.B[ri < NS ? ri : 0][0] : 0.0; BE1[i] = (NU > 1 && ri < NS) ? Pl.B[ri < NS ? ri : 0][NU > 1 ? 1 : 0] : 0.0;
+            BE0[i] = el_b(Pl, ri, 0); BE1[i] = NU > 1 ? el_b(Pl, ri, 1) : 0.0;
         }
-        const double RE0 = tc < NU ? Pl.R[0][tc] : 0.0, RE1 = (NU > 1 && tc < NU) ? Pl.R[NU > 1 ? 1 : 0][tc] : 0.0;
+        const double RE0 = el_r(Pl, 0, tc), RE1 = NU > 1 ? el_r(Pl, 1, tc) : 0.0;
         const double Ir = tr == tc ? 1.0 : 0.0;
         // barrier weights: sigma_z on the diagonal of P's diagonal tiles, sigma_u[r] on the diagonal of R~, sigma_u[i] at (., i) of broadcast row i
         const double *q_sz[SB];
@@ -530,8 +566,7 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         const int stpf = st_f ? PD : 0;
         double Pm[SB][SB], PC[SB];
         MPC_UNROLL for (int i = 0; i < SB; i++) {
-            const int ri = 4 * i + tr;
-            MPC_UNROLL for (int j = 0; j < SB; j++) { const int cj = 4 * j + tc; Pm[i][j] = (ri < NS && cj < NS) ? Pl.Pf[ri < NS ? ri : 0][cj < NS ? cj : 0] : 0.0; }
+            MPC_UNROLL for (int j = 0; j < SB; j++) Pm[i][j] = el_p(Pl, 4 * i + tr, 4 * j + tc);
             PC[i] = 0.0;
         }
         constexpr int NF = 2 * SB + 4 + (LTV ? 3 : 0);      // sigma_z[SB] sigma_u s0 s1 hu hz[SB] (a b bt)
@@ -1060,13 +1095,13 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
         bool any_on = false;
         MPC_UNROLL for (int j = 0; j < NJ; j++) any_on = any_on || (PAIR ? __any(S[j].on) != 0 : S[j].on);
         if (!any_on) break;      // wave-uniform: every instance has its verdict
-        __syncthreads();
+        wave_lds_sync();
         pd_min = 1.0;
         tile_factor();
-        __syncthreads();
+        wave_lds_sync();
         MPC_TSTAMP(2);
         tile_forward();
-        __syncthreads();
+        wave_lds_sync();
         MPC_TSTAMP(3);
         {
             const unsigned long long bad = __ballot(((lane >> 2) & 3) < NI && !(pd_min > 0.0));      // a Lambda lost definiteness: the instance stops as infeasible
@@ -1120,13 +1155,13 @@ __device__ __forceinline__ void wv_solve(const PT &P, double *T, const double *q
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        __syncthreads();
+        wave_lds_sync();
         MPC_TSTAMP(4);
         tile_rhs();
-        __syncthreads();
+        wave_lds_sync();
         MPC_TSTAMP(5);
         tile_forward();
-        __syncthreads();
+        wave_lds_sync();
         MPC_TSTAMP(3);
         // ================= element-wise: corrector step length, step; then the next iterate's residuals / gradients =====
         MPC_UNROLL for (int j = 0; j < NJ; j++) {
@@ -1251,7 +1286,7 @@ __device__ __forceinline__ void kalman_row16(const PT &P, int r, bool slot_on, d
         MPC_UNROLL for (int j = 0; j < NE; j++) Pr[j] = kp[p_off + rr * NE + j];
         MPC_UNROLL for (int j = 0; j < NY; j++) { double a = 0.0; MPC_UNROLL for (int l = 0; l < NE; l++) a += Pr[l] * P.Ca[j][l]; PCt[j] = a; }
         if (row) { MPC_UNROLL for (int j = 0; j < NY; j++) xch[r * NY + j] = PCt[j]; }
-        __syncthreads();
+        wave_lds_sync();
         double all[NE][NY], S[NY][NY];
         MPC_UNROLL for (int l = 0; l < NE; l++) { MPC_UNROLL for (int j = 0; j < NY; j++) all[l][j] = xch[l * NY + j]; }
         MPC_UNROLL for (int i = 0; i < NY; i++) { MPC_UNROLL for (int j = 0; j < NY; j++) { double a = P.Rkf[i][j]; MPC_UNROLL for (int l = 0; l < NE; l++) a += P.Ca[i][l] * all[l][j]; S[i][j] = a; } }
@@ -1264,7 +1299,7 @@ __device__ __forceinline__ void kalman_row16(const PT &P, int r, bool slot_on, d
         MPC_UNROLL for (int j = 0; j < NE; j++) { double a = 0.0; MPC_UNROLL for (int l = 0; l < NE; l++) a += Pc[l] * P.Aa[j][l]; U[j] = a; }
         double *xu = xch + NE * NY;
         if (row) { MPC_UNROLL for (int j = 0; j < NE; j++) xu[r * NE + j] = U[j]; }
-        __syncthreads();
+        wave_lds_sync();
         double Pn[NE];
         MPC_UNROLL for (int j = 0; j < NE; j++) Pn[j] = e[RT::E_Q + j];
         MPC_UNROLL for (int l = 0; l < NE; l++) { const double al = e[RT::E_A + l]; MPC_UNROLL for (int j = 0; j < NE; j++) Pn[j] += al * xu[l * NE + j]; }
@@ -1276,7 +1311,7 @@ __device__ __forceinline__ void kalman_row16(const PT &P, int r, bool slot_on, d
     MPC_UNROLL for (int l = 0; l < NY; l++) v += Kr[l] * innov[l];                                     // :303-306
     if (P.has_dsat && r >= NX) v = dmin(dmax(v, e[RT::E_DMIN]), e[RT::E_DMAX]);                     // MPC_code.py:655-668
     xi_new = v;
-    __syncthreads();      // everybody has read the old xi
+    wave_lds_sync();      // everybody has read the old xi
     if (row) kp[xi_off + r] = v;
 }
 
@@ -1384,6 +1419,8 @@ __device__ __forceinline__ int target_row16(const PT &P, int r, const double *ta
             else if (lmax > kInfeasZ * gscale || !(fabs(mu) < 1.0e300)) { status = kInfeasible; on = false; }
             else if (it == P.max_iter) { status = kMaxIter; on = false; }
         }
+        // the last instance of the wave has its verdict: the Newton direction below would update nothing (in a steady-state step all four end in the same trip)
+        if (!__any(on ? 1 : 0)) break;
         double Ht[NR][NR];
         MPC_UNROLL for (int i = 0; i < NR; i++) { MPC_UNROLL for (int j = 0; j <= i; j++) { const double a = P.Hr[i][j] + row16_sum(sig * Wr[i] * Wr[j]); Ht[i][j] = a; Ht[j][i] = a; } }
         const bool pd = sym_inverse<NR>(Ht);

@@ -6,7 +6,9 @@
 A loop is what lies between a backward branch and its target (the blocks from the target label to the branching one, summed in the
 manner of tools/isa_blocks.py); nested loops are reported each on its own.  Every instruction is one of VALU / MFMA / accvgpr / LDS /
 nop / wait / scratch / other; mfma_adjacent counts the matrix-core products whose next instruction is another product (no
-instruction issued in the gap between them).  Also printed: the kernel's register counts and private segment, and the totals of the whole kernel.
+instruction issued in the gap between them).  Counted next to the kinds, per loop and in total: vmem_load (global_load / flat_load /
+buffer_load: a vector-memory round trip), vmcnt_wait (an s_waitcnt with a vmcnt field: it waits for such a load, or for the acknowledgement
+of a store) and canon_max (v_max_f64 x, y, y: the copy that quiets an operand of a maximum or minimum).  Also printed: the kernel's register counts and private segment, and the totals of the whole kernel.
 The self-looping blocks that hold v_mfma_f64 are the tile sweeps of mpc_wave.hpp (tile_factor, tile_forward twice, tile_rhs)."""
 import collections
 import json
@@ -14,6 +16,7 @@ import re
 import sys
 
 KINDS = ("valu", "mfma", "accvgpr", "lds", "nop", "wait", "scratch", "other")
+EXTRA = ("vmem_load", "vmcnt_wait", "canon_max")      # counted on top of the kinds (each such instruction has a kind as well)
 
 
 def classify(op):
@@ -32,6 +35,20 @@ def classify(op):
     if op.startswith("v_"):
         return "valu"
     return "other"
+
+
+def extras(op, text):
+    """the EXTRA counters one instruction line adds to"""
+    out = []
+    if op.startswith(("global_load", "flat_load", "buffer_load")):
+        out.append("vmem_load")
+    if op.startswith("s_waitcnt") and "vmcnt" in text:
+        out.append("vmcnt_wait")
+    if op.startswith("v_max_f64"):
+        args = [a.strip() for a in text[len(op):].split(",")]
+        if len(args) == 3 and args[1] == args[2]:
+            out.append("canon_max")
+    return out
 
 
 def kernel_lines(lines, pat):
@@ -57,6 +74,8 @@ def parse_blocks(body):
         kind = classify(op)
         blocks[-1][1][kind] += 1
         blocks[-1][1]["instrs"] += 1
+        for x in extras(op, t):
+            blocks[-1][1][x] += 1
         if kind == "mfma" and prev == "mfma":
             blocks[-1][1]["mfma_adjacent"] += 1
         prev = kind
@@ -75,7 +94,7 @@ def loops_of(blocks):
                 for b in blocks[index[tgt]:i + 1]:
                     tot.update(b[1])
                 out.append({"head": tgt, "tail": label, "blocks": i + 1 - index[tgt], "self_loop": tgt == label,
-                            **{k: tot[k] for k in ("instrs",) + KINDS + ("mfma_adjacent",)}})
+                            **{k: tot[k] for k in ("instrs",) + KINDS + ("mfma_adjacent",) + EXTRA}})
     return out
 
 
@@ -96,7 +115,7 @@ def analyse(path, pat):
     for b in blocks:
         tot.update(b[1])
     loops = loops_of(blocks)
-    return {"kernel": name, "resources": resources(lines, name), "total": {k: tot[k] for k in ("instrs",) + KINDS},
+    return {"kernel": name, "resources": resources(lines, name), "total": {k: tot[k] for k in ("instrs",) + KINDS + EXTRA},
             "tile_sweeps": [l for l in loops if l["self_loop"] and l["mfma"]], "loops": loops}
 
 
